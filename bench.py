@@ -1,14 +1,18 @@
 """bench.py -- 512x512 images/s training centerOffsetRes10 (bf16) on N MI355X, one process per GPU.
 
-python bench.py --gpus N --steps K --warmup W
+python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N>1: started under torch.distributed.run (WORLD_SIZE set; it must equal N), or by itself -- without
 WORLD_SIZE the script launches N rank processes of itself (one per GPU) before touching the GPU.
 
 A step = NetworkFactory.train on one synthetic batch of 32 tiles per GPU (zero_grad, forward,
 CenterNetLoss, backward incl. the RCCL gradient all-reduce + SyncBN statistics, Adam) with the
-inputs already resident in HBM.  Prints ONE JSON line on rank 0 with the metric, the roofline of
-the dominant kernel (HIP events on the launch stream) and the CPU-oracle baseline.
+inputs already resident in HBM.  Prints ONE JSON line on rank 0 with the metric and the roofline of
+the dominant kernel (HIP events on the launch stream, recorded inside the timed steps).
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs (--dump-outputs) and prints the
+line.  --full adds what takes work of its own after the timed steps: the CPU-oracle baseline, the achievable-peak
+calibration, the per-class rooflines and, at N > 1, the exchange probe and the collective-free steps.
 """
 import argparse
 import json
@@ -41,6 +45,13 @@ def parse():
     ap.add_argument("--image-size", type=int, default=512,
                     help="tile size; 512 uses the synthetic SCD dataset plugin, other sizes N(0,1) tiles with "
                          "random sparse targets of the same layout (e.g. BASELINE configs[4]: Res50 at 1024)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the CPU-oracle baseline, the achievable-peak calibration, the "
+                         "per-class rooflines and (N > 1) the exchange probe and the collective-free steps; without it "
+                         "none of them runs and the options below that tune them have no effect")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed (loss, head outputs, gradients, "
+                         "updated parameters; rank 0's) as DIR/<name>.npy, float32")
     ap.add_argument("--cpu-baseline-steps", type=int, default=12)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--class-rooflines", type=int, default=None,
@@ -188,6 +199,42 @@ def heads_gemm_roofline(B, dtype_name, S=512, cin=256, hd=128, ods=(1, 4, 2), ke
             "traffic_note": None if traffic is not None else src,
             "algorithmic_bytes": algo_bytes, "flop_per_launch": flops, "avg_launch_ms": round(ms, 4),
             "launches_timed": n}
+
+
+DUMP_BUDGET_BYTES = 48 << 20       # --dump-outputs: all files together (float32), shared evenly among the arrays
+
+
+def _tensors(prefix, obj, out):
+    """Flatten nested lists / tuples / dicts of tensors into out[name] (names from the keys and positions)."""
+    if torch.is_tensor(obj):
+        out[prefix] = obj
+    elif isinstance(obj, dict):
+        for k in sorted(obj):
+            _tensors("%s_%s" % (prefix, k), obj[k], out)
+    elif isinstance(obj, (list, tuple)):
+        for i, v in enumerate(obj):
+            _tensors("%s%d" % (prefix, i), v, out)
+
+
+def dump_outputs(path, loss, outs, flat):
+    """--dump-outputs: what the last timed step handed back -- the loss, the model's head outputs, the gradients it
+    left and the parameters after its optimizer update -- one float32 <name>.npy each.  An array larger than its share
+    of DUMP_BUDGET_BYTES is written as a fixed sample of its flattened elements (seeded by its size alone, so two
+    builds sample the same positions)."""
+    import numpy as np
+    arrs = {}
+    _tensors("loss", loss, arrs)
+    _tensors("out", outs, arrs)
+    arrs["grad"] = flat.grad
+    arrs["param"] = flat.data
+    os.makedirs(path, exist_ok=True)
+    cap = DUMP_BUDGET_BYTES // 4 // len(arrs)
+    for name, t in arrs.items():
+        a = t.detach().float().cpu().numpy()
+        if a.size > cap:
+            idx = np.sort(np.random.RandomState(a.size & 0x7FFFFFFF).choice(a.size, cap, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), np.asarray(a, dtype=np.float32))
 
 
 def exchange_probe(model, dev, reps=50):
@@ -395,11 +442,16 @@ def main():
 
     prepare = getattr(lossfn, "prepare", None)       # CenterNetLoss: tells the heads where the loss will gather
 
+    last = {}                                        # --dump-outputs: the newest step's model outputs
+
     def train_step():
         opt.zero_grad()
         if prepare is not None:
             prepare(ys)
-        loss, _ = lossfn(model(x, decode=False), ys)
+        outs = model(x, decode=False)
+        if args.dump_outputs:
+            last["outs"] = outs
+        loss, _ = lossfn(outs, ys)
         loss = mean_backward(loss)              # loss.mean(); loss.backward()
         opt.step()
         return loss
@@ -421,7 +473,7 @@ def main():
         step = train_step
 
     probe = None
-    if world > 1:
+    if world > 1 and args.full:
         probe = exchange_probe(model, dev)
 
     # with the graph: 2 eager steps, the capture step and the first replay of the second copy are warm-up
@@ -456,8 +508,10 @@ def main():
     elapsed = t.item()
     final_loss = loss.item()
     ops.SyncCounter.per_step = ops.SyncCounter.calls / args.steps
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, last.get("outs"), opt.flat())
     local_ms = None
-    if world > 1:
+    if world > 1 and args.full:
         # after the timed region: the same steps with every collective off (FlatDDP.local_only), max over ranks --
         # what the exchange (gradient buckets, SyncBN, buffer broadcast) adds to each rank's step, measured in-run
         with model.local_only():
@@ -476,7 +530,7 @@ def main():
     ncls = args.class_rooflines if args.class_rooflines is not None else (
         0 if (args.model == "centerOffsetRes10" and S == 512) else 5)
     classes = None
-    if ncls > 0 and world == 1:
+    if args.full and ncls > 0 and world == 1:
         # after the timed region: per-class kernel time and algorithmic work over ncls more steps (events around every
         # launch of a class, on its stream; classes on the two streams overlap, so their times do not add up to the step)
         ops.ClassTimer.on = True
@@ -571,7 +625,7 @@ def main():
                 # flat-gradient all-reduce when the buckets do not overlap the backward
                 probe["syncbn_calls_per_step"] = ops.SyncCounter.per_step
                 line["exchange"]["probe"] = probe
-        if world == 1 and not args.no_calib and dtype != torch.float32:
+        if args.full and world == 1 and not args.no_calib and dtype != torch.float32:
             # the bf16 MFMA rate this box sustains (bare 16x16x32 loops on random operands, 2 waves per SIMD, after
             # 2.5 s of back-to-back launches: MI355X_MICROARCH.md "DVFS give-back"), beside the 2.5 PF/s nameplate
             from scdhip import calib
@@ -586,7 +640,7 @@ def main():
                                        "source": "scd_calib_mfma_peak: 16x16x32 bf16 MFMA loops on random operands, "
                                                  "2 waves/SIMD, in-kernel clock from s_memtime / s_memrealtime"}
             line["step_mfma_frac_achievable"] = round(value * executed / 1e3 / (world * pa), 4)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args.cpu_baseline_steps)
         print(json.dumps(line), flush=True)
     if world > 1:

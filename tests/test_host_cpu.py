@@ -225,6 +225,33 @@ def test_bench_refuses_world_size_mismatch():
     assert out.returncode != 0 and b"WORLD_SIZE" in out.stdout
 
 
+def test_bench_dump_outputs_writes_float32_within_budget(tmp_path, monkeypatch):
+    """bench.dump_outputs: one float32 <name>.npy per array of the last step (nested outputs named by key / position);
+    an array above its share of the budget is a sample of its elements, the same positions on every call."""
+    import types
+
+    import numpy as np
+    import torch
+
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 5 * 4 * 100)        # 5 arrays, 100 elements each
+    big = torch.arange(1000, dtype=torch.float32)
+    outs = [{"heatmap": torch.ones(2, 1, 4, 4, dtype=torch.bfloat16), "regr": torch.full((3,), 2.0, dtype=torch.float64)}]
+    flat = types.SimpleNamespace(grad=big * 2, data=big)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), torch.tensor(1.5), outs, flat)
+    got = {f: np.load(str(tmp_path / "a" / f)) for f in sorted(os.listdir(str(tmp_path / "a")))}
+    assert sorted(got) == ["grad.npy", "loss.npy", "out0_heatmap.npy", "out0_regr.npy", "param.npy"]
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert got["loss.npy"].shape == () and got["loss.npy"] == 1.5
+    assert got["out0_heatmap.npy"].shape == (2, 1, 4, 4) and (got["out0_regr.npy"] == 2.0).all()
+    p = got["param.npy"]
+    assert p.shape == (100,) and (np.diff(p) > 0).all() and (got["grad.npy"] == 2 * p).all()
+    assert sum(a.nbytes for a in got.values()) <= 5 * 4 * 100
+    for f, a in got.items():
+        np.testing.assert_array_equal(a, np.load(str(tmp_path / "b" / f)))
+
+
 def test_resume_schedule_pops_past_milestones():
     """resuming past a milestone keeps the later decays (the reference skips them)."""
     from models.networkFactory import resumeSchedule
