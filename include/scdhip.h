@@ -381,6 +381,21 @@ int scd_slide_tiles(const uint8_t* rgb, int H, int W, int C, int tile, int strid
                     int padTB, int fix, float* out, void* workspace, void* stream);
 int scd_slide_detections(const float* decoded, int T, int K, int stride, int padLR, int padTB, int clipV, float thr,
                          int* xy, double* ratio, int* count, void* stream);
+/* ---- building a `.d` archive (preprocess.py; datasets/preprocessor/scdManual.py:133-186,
+ * datasets/argumentations.py:148-159) ----
+ * scd_slide_rotate_clips: RGB slide (H,W,C>=3) u8 on the device -> out (R, nx*ny, tile, tile) fp32, nx = (W+left+
+ * right)/tile, ny = (H+top+bottom)/tile, clip index x*ny + y: for each of the R angles (host doubles, degrees,
+ * 1 <= R <= 16) the grayscale slide fp32((0.30 c0 + 0.59 c1) + 0.11 c2), torch-'reflect' padded by the margins,
+ * rotated about its centre as argumentations.rotate(MirrorPadding, Bilinear) does (a second reflect pad to the
+ * diagonal, torchvision's tensor rotate: bilinear, zeros outside, align_corners = False; coordinates in fp64,
+ * interpolation in fp32) and cut into tiles.  SCD_ERR_ARG and no launch when H < 2 or W < 2, a padded dimension is
+ * no multiple of tile, a margin is negative or >= its dimension, the diagonal padding >= the padded dimension,
+ * C < 3, R outside 1..16, tile % 4 != 0, out has 2^31 elements or more, or there are more than 65535 clips per
+ * rotation (the grid's y limit).  workspace: scd_slide_rotate_workspace(H, W) bytes (the
+ * grayscale plane shared by the R rotations). */
+size_t scd_slide_rotate_workspace(int H, int W);
+int scd_slide_rotate_clips(const uint8_t* rgb, int H, int W, int C, int left, int top, int right, int bottom,
+                           int tile, const double* angles, int R, float* out, void* workspace, void* stream);
 /* ---- decode (centerNetOffset.py:219-251, utility.py:87-118) ---- */
 size_t scd_decode_workspace(int N, int HW);
 int scd_decode_topk(const float* heat, int N, int H, int W, int K, const float* offset, int od_off,

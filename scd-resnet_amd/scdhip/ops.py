@@ -1560,3 +1560,41 @@ def slide_detections(decoded, stride, pad_lr, pad_tb, clip_v, threshold=0.3):
            ptr(ratio), ptr(count), stream())
     n = int(count.item())
     return xy[:n], ratio[:n]
+
+
+def slide_rotate_geometry(H, W, margins, tile):
+    """(nx, ny) clips of a slide cut by slide_rotate_clips: the margin-padded frame over the tile size."""
+    l, t, r, b = [int(m) for m in margins]
+    return (W + l + r) // tile, (H + t + b) // tile
+
+
+def slide_rotate_clips(rgb, margins, tile, angles, resample="bilinear"):
+    """preprocess.py's clips on the GPU (scd_slide_rotate_clips; scdManual.py:133-186, argumentations.py:148-159):
+    RGB slide (H,W,C>=3) uint8 -> (R, nx*ny, tile, tile) float32, clip index x*ny + y: the grayscale slide
+    reflect-padded by margins (left, top, right, bottom), rotated about its centre by each of the R <= 16 angles
+    (degrees; MirrorPadding, Bilinear) and cut into tiles.  The rotation is torchvision's tensor rotate restated
+    (affine_grid / grid_sample, align_corners=False, zeros outside the diagonal-padded frame); that the restatement
+    equals real torchvision bit for bit has not been measured (torchvision is no dependency of this project).
+    Only bilinear resampling exists (the reference's ResampleMode.NearestNeighbour / Bicubic raise)."""
+    _need_gpu(rgb)
+    if resample != "bilinear":
+        raise RuntimeError("slide_rotate_clips: only bilinear resampling is implemented, not %r" % (resample,))
+    rgb = rgb.contiguous()
+    if rgb.dtype != torch.uint8 or rgb.dim() != 3:
+        raise RuntimeError("slide_rotate_clips: (H, W, C) uint8 slide expected")
+    H, W, C = rgb.shape
+    l, t, r, b = [int(m) for m in margins]
+    tile = int(tile)
+    ang = [float(a) for a in angles]
+    R = len(ang)
+    nx, ny = slide_rotate_geometry(H, W, (l, t, r, b), max(tile, 1))
+    elems = R * nx * ny * tile * tile
+    # refused here, before the output is sized from them; the library checks these and every other argument
+    # (margins, divisibility, the diagonal padding, C) itself, after the buffers below exist
+    if not 1 <= R <= 16 or tile < 4 or not 0 < elems < 2 ** 31:
+        L.check(9001, "scd_slide_rotate_clips")
+    out = torch.empty(R, nx * ny, tile, tile, device=rgb.device)
+    ws = torch.empty(max(4, L.lib().scd_slide_rotate_workspace(H, W)), dtype=torch.uint8, device=rgb.device)
+    L.call("scd_slide_rotate_clips", ptr(rgb), H, W, C, l, t, r, b, tile, (ctypes.c_double * R)(*ang), R,
+           ptr(out), ptr(ws), stream())
+    return out

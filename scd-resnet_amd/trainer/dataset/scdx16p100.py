@@ -1,4 +1,9 @@
-"""`.d` archive dataset plugin `scdx16p100` (datasets/scds/scdx16p100.py of the reference).
+"""`.d` archive dataset plugin `scdx16p100` (datasets/scds/scdx16p100.py of the reference), and the
+one implementation behind the 25 plugins `scdx{N}p{M}` of this package: the reference's
+datasets/scds/scdx{1,4,8,12,16}p{5,10,25,50,100}.py differ in three constants only (ARGUMENTRATIO = N, how many of
+the 16 preprocess rotations per slide to keep; PARTITION = M / 100, the share of the kept tiles to use; TRAINSUBSET =
+'train{N}p{M}', the split profile's key), so each of the other 24 modules is `globals().update(family(N, M))`.  The
+implementation stays in this module, which tests/golden/make_golden_scd.py loads by file path outside the package.
 
 The on-disk format is the reference's (scdx16p100.py:64-93; written by preprocess.py:78-109 through a profile's
 generateArchieve): a zip holding
@@ -9,9 +14,10 @@ generateArchieve): a zip holding
 Constructor, split rules and sample format are the reference's:
   * samples index FSI x ARGUM x CLIP = 130 x 16 x 24 raw positions, kept when argum < ARGUMENTRATIO, shuffled with
     Python's `random` (unseeded, as the reference), cut to PARTITION (:143-158);
-  * no split profile: the first TESTSET shuffled positions become the validation set, the rest `train16p100`;
-    with a profile: its `train16p100` list, or everything not in its `validation` list (:160-180); the profile
-    is written back to defaultConfig.dirDataSplitProfile (:264-266);
+  * no split profile: the first TESTSET shuffled positions of that cut order become the validation set (even
+    when that leaves no training tile), the rest TRAINSUBSET; with a profile: its TRAINSUBSET list, or the cut
+    order minus its `validation` list, added to the profile under TRAINSUBSET (:160-180); the profile is written
+    back to defaultConfig.dirDataSplitProfile (:264-266);
   * validation set: normalize (no augmentation), heat / mask / regr / locs / inds with the objects' centres
     truncated to integers (:188-262), served in validationBatchSize slices by getValidationSet (:381-414);
   * __getitem__(i): reshuffle at i == 0, x / y flips (numpy.random.uniform() > 0.5), normalize, variance jitter
@@ -45,7 +51,11 @@ TRAINSUBSET = 'train16p100'
 FSI, ARGUM, CLIP = 130, 16, 24
 NOISESV, JITTERSV = 0.05, 0.05
 
-__all__ = ["SCD", "dataset", "writeArchive", "readArchive", "splitOrder"]
+__all__ = ["SCD", "dataset", "writeArchive", "readArchive", "splitOrder", "family"]
+# what a family() plugin takes from this module as it stands, beside its own three constants, SCD / dataset and
+# splitOrder: the reference modules' other constants and the archive functions
+FAMILY_NAMES = ("MAXTAGLEN", "TARGETSIZE", "HEATMAPSIZE", "THRESHOLDIOU", "TESTSET", "REALTIMETEST", "FSI", "ARGUM",
+                "CLIP", "NOISESV", "JITTERSV", "writeArchive", "readArchive")
 
 
 def writeArchive(path, names, samples, locs):
@@ -115,34 +125,35 @@ def _pack_locs(bounds_list, trunc):
     return locs, counts
 
 
-def splitOrder(count, dataSplit=None):
+def splitOrder(count, dataSplit=None, ratio=ARGUMENTRATIO, partition=PARTITION, subset=TRAINSUBSET):
     """Training order and split profile (scdx16p100.py:143-180): FSI x ARGUM x CLIP positions (only the first
-    `count` of a smaller test archive) kept when argum < ARGUMENTRATIO, shuffled with Python's global `random`,
-    cut to PARTITION; then the split.  Returns (order, dataProfile)."""
+    `count` of a smaller test archive) kept when argum < ratio, shuffled with Python's global `random`, cut to
+    partition; then the split, the training ids under the profile's key `subset`.  Returns (order, dataProfile)."""
     total = min(FSI * ARGUM * CLIP, count)
-    order = [i for i in range(total) if (i // CLIP) % ARGUM < ARGUMENTRATIO]
+    order = [i for i in range(total) if (i // CLIP) % ARGUM < ratio]
     shuffle(order)
-    order = order[0: int(len(order) * PARTITION)]
+    order = order[0: int(len(order) * partition)]
     if dataSplit is None:
         _log("The Data Split Profile Do Not Exist, We Randomly Select 10 pct. of Samples as Validation Set.")
         shuffle(order)
         numValidation = round(TESTSET)
         profile = {'validation': order[0:numValidation]}
         order = order[numValidation:]
-        profile[TRAINSUBSET] = order
+        profile[subset] = order
     else:
         _log("Extracting Validation Set from Data Split Profile ...")
         profile = dataSplit
-        if TRAINSUBSET in profile.keys():
-            order = profile[TRAINSUBSET]
+        if subset in profile.keys():
+            order = profile[subset]
         else:
             valid = set(profile['validation'])
             order = [x for x in order if x not in valid]
-            profile[TRAINSUBSET] = order
+            profile[subset] = order
     return order, profile
 
 
 class SCD(Dataset):
+    ARGUMENTRATIO, PARTITION, TRAINSUBSET = ARGUMENTRATIO, PARTITION, TRAINSUBSET
 
     def __init__(self, zipPath, useGPU, dataSplit=None):
         from configuration import defaultConfig
@@ -152,7 +163,8 @@ class SCD(Dataset):
         self.useGPU = useGPU
         self.device = _device(useGPU)
 
-        self.order, self.dataProfile = splitOrder(len(self.names), dataSplit)
+        self.order, self.dataProfile = splitOrder(len(self.names), dataSplit, ratio=self.ARGUMENTRATIO,
+                                                  partition=self.PARTITION, subset=self.TRAINSUBSET)
         self.count = len(self.order)
 
         self._buildValidation()
@@ -258,3 +270,21 @@ class SCD(Dataset):
 
 
 dataset = SCD
+
+
+def family(ratio, percent):
+    """The names of plugin module `scdx{ratio}p{percent}`: this module's, with the three constants, the SCD class and
+    splitOrder bound to (ARGUMENTRATIO, PARTITION, TRAINSUBSET) = (ratio, percent / 100, 'train{ratio}p{percent}')."""
+    if ratio not in (1, 4, 8, 12, 16) or percent not in (5, 10, 25, 50, 100):
+        raise ValueError("no reference plugin scdx%sp%s" % (ratio, percent))
+    partition, subset = percent / 100.0, "train%dp%d" % (ratio, percent)
+    consts = {"ARGUMENTRATIO": ratio, "PARTITION": partition, "TRAINSUBSET": subset}
+    cls = type("SCD", (SCD,), dict(consts, __module__="trainer.dataset.scdx%dp%d" % (ratio, percent)))
+
+    def split(count, dataSplit=None):
+        return splitOrder(count, dataSplit, ratio=ratio, partition=partition, subset=subset)
+    split.__doc__ = splitOrder.__doc__
+    names = {name: globals()[name] for name in FAMILY_NAMES}
+    names.update(consts, SCD=cls, dataset=cls, splitOrder=split,
+                 __all__=["SCD", "dataset", "writeArchive", "readArchive", "splitOrder"])
+    return names
