@@ -77,6 +77,15 @@ int scd_conv_gemm_bnbwd(int dtype, const void* x, const void* w, void* y, int N,
                         int Wo, int Co, int in_stride, int out_stride, int wrow, int nphase,
                         const scd_gemm_phase* phases, const void* bn_y, const float* mean, const float* invstd,
                         const float* relu_scale, const float* relu_shift, double* bn_stats, void* stream);
+/* Folded-BatchNorm inference conv: y[pix,co] = act(acc + bias[co] + res[pix,co]) with acc the gather-GEMM of
+ * scd_conv_gemm.  res is NHWC (N,Ho,Wo,Co) in dtype, read at the output pixel's own offset; the sum is formed in fp32
+ * from the unrounded accumulator, the ReLU follows the add and the result is rounded once to dtype at the store
+ * (scd_conv_gemm's `accumulate` adds after the ReLU and a first rounding).  bias and res may each be NULL; with
+ * res == NULL the result is that of scd_conv_gemm(..., bias, NULL, relu, 0, ...) bit for bit.  res == y is
+ * SCD_ERR_ARG.  Shapes and alignment as scd_conv_gemm; no statistics. */
+int scd_conv_gemm_res(int dtype, const void* x, const void* w, void* y, const float* bias, const void* res, int N,
+                      int Hi, int Wi, int Ci, int Ho, int Wo, int Co, int in_stride, int out_stride, int wrow,
+                      int relu, int nphase, const scd_gemm_phase* phases, void* stream);
 /* Head convolution with the CenterNet tails fused into the epilogue: hid = relu(conv3x3(x, w) + bias)
  * (N,H,W,nh*128) NHWC and, from the same tile, outs[h] (N,od[h],H,W) fp32 = w1[h] . hid_h + b1[h].
  * Replaces the three terminal Sequentials (centerNetOffset.py:106-110) in one launch; w is the

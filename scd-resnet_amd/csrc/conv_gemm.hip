@@ -84,6 +84,10 @@ struct GemmParams {
     unsigned long long* stamps;
     // duo kernel: workgroups [duo_ncu, 2 duo_ncu) sleep duo_delay x 8K cycles before their first tile
     int duo_ncu, duo_delay;
+    // scd_conv_gemm_res (RES instantiations): residual (N, Ho, Wo, Co) in the output's type, added to the fp32
+    // accumulator + bias before the ReLU and the one rounding at the store; ybytes is its buffer range
+    const char* res;
+    int resmode;       // 1: the call is scd_conv_gemm_res (the fast kernels' bias / residual / ReLU variants may take it)
 };
 
 #ifndef SCD_STAMP
@@ -158,7 +162,7 @@ __device__ __forceinline__ uint4 bload(__amdgpu_buffer_rsrc_t r, int off) {
 // Shared GEMM epilogue (NT = 2*BM threads, waves of 64x64 outputs, WN waves along N): bias / ReLU in
 // registers, the wave's tile staged in LDS, coalesced 16-B NHWC stores (+= when accumulating), BN
 // channel sums into fp64 replicas, and optionally the fused 1x1 head tails (n-tile t == head t).
-template <typename T, int BM, int BN, int WN, bool HEADS, bool BNB = false>
+template <typename T, int BM, int BN, int WN, bool HEADS, bool BNB = false, bool RES = false>
 __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, f32x4 (&acc)[4][4], char* smem, int tid, int bid,
                                               int mt, int nt, int M, int QQ, const scd_gemm_phase& ph) {
     constexpr int ESZ = sizeof(T);
@@ -182,8 +186,9 @@ __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, f32x4 (&acc)[
         for (int r = 0; r < 4; ++r) { csum[b][r] = 0.f; csq[b][r] = 0.f; }
     // BN-backward mode (BNB: 16-bit types, scd_conv_gemm_bnbwd): output pixel of each of the lane's 4 rows
     // (-1 past the end); a separate instantiation, so the other kernels keep their register allocation
+    // (RES, scd_conv_gemm_res: the same pixels address the residual; also separate instantiations)
     int pix[4];
-    if constexpr (BNB) {
+    if constexpr (BNB || RES) {
 #pragma unroll
         for (int a = 0; a < 4; ++a) {
             const int m = mt * BM + wm * 64 + a * 16 + l16;
@@ -233,6 +238,32 @@ __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, f32x4 (&acc)[
                 }
             }
         }
+        // RES: the lane's 4 channels of the residual at each of its 4 pixels, in the accumulator layout (8-B / 16-B
+        // loads; the four channel blocks of a pixel share one 128-B line), as fp32
+        float rv[RES ? 4 : 1][4];
+        if constexpr (RES) {
+            const bool okc = col0 < p.Co;
+            const int cl = okc ? col0 : 0;
+#pragma unroll
+            for (int a = 0; a < 4; ++a) {
+                const bool ok = pix[a] >= 0 && okc;
+                const char* src = p.res + ((long)(ok ? pix[a] : 0) * p.Co + cl) * ESZ;
+                if constexpr (ESZ == 2) {
+                    uint2 raw;
+                    if constexpr (SELF) { const uint2 l = *(const uint2*)src; raw = ok ? l : make_uint2(0, 0); }
+                    else raw = ok ? *(const uint2*)src : make_uint2(0, 0);
+                    const unsigned rw[2] = {raw.x, raw.y};
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) rv[a][r] = h16_word_half(rw[r >> 1], r & 1);
+                } else {
+                    const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+                    float4 raw;
+                    if constexpr (SELF) { const float4 l = *(const float4*)src; raw = ok ? l : z4; }
+                    else raw = ok ? *(const float4*)src : z4;
+                    rv[a][0] = raw.x; rv[a][1] = raw.y; rv[a][2] = raw.z; rv[a][3] = raw.w;
+                }
+            }
+        }
 #pragma unroll
         for (int a = 0; a < 4; ++a) {
             const int m = mt * BM + wm * 64 + a * 16 + l16;
@@ -241,6 +272,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, f32x4 (&acc)[
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     v[r] = acc[a][b][r] + bias[r];
+                    if constexpr (RES) v[r] += rv[a][r];
                     if (p.relu) v[r] = fmaxf(v[r], 0.f);
                     if constexpr (SELF) {
                         // a select, not a branch region (the sums never hold -0: adding +0 past M leaves them unchanged)
@@ -381,7 +413,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, f32x4 (&acc)[
 // four waves each run the 128x128 tile over one half of the K stages in their own double-buffered LDS
 // stages (8 waves per CU instead of 4, no partial sums through HBM); group 1 hands its accumulators to group
 // 0 through LDS and exits (S_BARRIER then waits on the surviving waves only), group 0 runs the epilogue.
-template <typename T, int BM, int BN, bool HEADS, bool BNB = false, int KS = 1>
+template <typename T, int BM, int BN, bool HEADS, bool BNB = false, int KS = 1, bool RES = false>
 __global__ __launch_bounds__(256 * KS, 2 / KS) void conv_gemm_kernel(GemmParams p) {
     static_assert(KS == 1 || KS == 2, "split K by 1 or 2");
     constexpr int ESZ = sizeof(T);
@@ -587,7 +619,7 @@ __global__ __launch_bounds__(256 * KS, 2 / KS) void conv_gemm_kernel(GemmParams 
         __syncthreads();
     }
 
-    gemm_epilogue<T, BM, BN, WN, HEADS, BNB>(p, acc, smem, tid, bid, mt, nt, M, QQ, ph);
+    gemm_epilogue<T, BM, BN, WN, HEADS, BNB, RES>(p, acc, smem, tid, bid, mt, nt, M, QQ, ph);
 }
 
 // -------------------------------------------------------------------------------------
@@ -639,9 +671,15 @@ __device__ __forceinline__ void dma16_asm(__amdgpu_buffer_rsrc_t r, const char* 
 // outputs bit-identical.  The BN-backward-sum variant
 // is not built for them (its operand loads in this layout spill registers): scd_conv_gemm_bnbwd then runs this
 // kernel's plain input gradient and the separate scd_bn_bwd_reduce.
-template <int WO, bool FLIP, bool BNB>
+// RES (scd_conv_gemm_res, forward): bias, residual and ReLU on the fp32 accumulators before they are rounded.  The
+// lane's 8 residual pieces of a tile (8 B per accumulator fragment: the tile is one contiguous NHWC block) are buffer
+// loads issued behind the next tile's row DMAs, before the tile's MFMAs, so they land under the MFMAs and are
+// covered by the full wait that closes the tile anyway; a NULL residual is a zero-length buffer (the loads return
+// zeros: no branch).  Sum order as the shared epilogue's -- (acc + bias) + res -- so the outputs are its bits.
+template <int WO, bool FLIP, bool BNB, bool RES = false>
 __global__ __launch_bounds__(512, 1) void conv_gemm_l1p_kernel(GemmParams p, int run) {
     typedef h16 T;
+    static_assert(!(RES && (FLIP || BNB)), "bias / residual / ReLU epilogue: forward only");
     constexpr int TR = WO >= 256 ? 1 : 256 / WO;  // output rows per tile
     constexpr bool DIRECT = WO == 256;            // no staging buffer: stores from the accumulators
     static_assert(!(DIRECT && BNB), "256-pixel rows: BN-backward sums by the separate reduction");
@@ -711,7 +749,16 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_l1p_kernel(GemmParams p, int
     // 0..127 (channel tid & 63, sum tid >> 6) add them in a fixed order, so the sums are deterministic
     __shared__ float bnred[8 * 64 * 2];
     float bnsum = 0.f;
-    const bool fwd_stats = !BNB && p.stats;
+    const bool fwd_stats = !BNB && !RES && p.stats;
+    float bz[2][4];
+    __amdgpu_buffer_rsrc_t rrs = xrs;
+    if constexpr (RES) {
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) bz[b][q] = p.bias ? p.bias[32 * chh + 16 * b + 4 * lg + q] : 0.f;
+        rrs = __builtin_amdgcn_make_buffer_rsrc((void*)(p.res ? p.res : p.x), (short)0, p.res ? p.ybytes : 0, 0x00020000);
+    }
     const int cc = tid & 7;                       // store phase: this thread's 8-channel chunk
 
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -720,6 +767,16 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_l1p_kernel(GemmParams p, int
     for (int i = 0; i < run; ++i) {
         const int r = r0 + i * TR;
         if (i + 1 < run) dma_rows(r + TR + 1, TR);            // the next tile's new rows, into free ring slots
+        uint2 rq[RES ? 4 : 1][2];
+        if constexpr (RES) {
+            const int rb = (n * p.Ho + r) * p.Wo * 64 * 2;     // the tile's byte offset (< 2^31: checked at launch)
+#pragma unroll
+            for (int a = 0; a < 4; ++a)
+#pragma unroll
+                for (int b = 0; b < 2; ++b)
+                    rq[a][b] = __builtin_bit_cast(uint2, __builtin_amdgcn_raw_buffer_load_b64(
+                        rrs, rb + ((64 * pw + 16 * a + l16) * 64 + 32 * chh + 16 * b + 4 * lg) * 2, 0, 0));
+        }
         f32x4 acc[4][2];
 #pragma unroll
         for (int a = 0; a < 4; ++a)
@@ -744,6 +801,21 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_l1p_kernel(GemmParams p, int
                         acc[a][b] = mfma_16x16x32_h16(__builtin_bit_cast(h16x8, wreg[t][s][b]),
                                                                             af[a], acc[a][b]);
             }
+        }
+        if constexpr (RES) {
+#pragma unroll
+            for (int a = 0; a < 4; ++a)
+#pragma unroll
+                for (int b = 0; b < 2; ++b) {
+                    const unsigned rw[2] = {rq[a][b].x, rq[a][b].y};
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        float v = acc[a][b][q] + bz[b][q];
+                        v += h16_word_half(rw[q >> 1], q & 1);
+                        if (p.relu) v = fmaxf(v, 0.f);
+                        acc[a][b][q] = v;
+                    }
+                }
         }
         if constexpr (DIRECT && L1P_SWAP) {
             // the tile is row r of image n: lane's pixel 64pw + 16a + l16 is its column.  The two channel blocks
@@ -902,7 +974,7 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_l1p_kernel(GemmParams p, int
     }
 }
 
-template <bool HEADS, bool BNB = false>
+template <bool HEADS, bool BNB = false, bool RES = false>
 __global__ __launch_bounds__(512, 1) void conv_gemm_ring_kernel(GemmParams p) {
     typedef h16 T;
     constexpr int BM = 256, BN = 128, WN = 2, BK = 64, EPC = 8;
@@ -1041,7 +1113,7 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_ring_kernel(GemmParams p) {
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    gemm_epilogue<T, BM, BN, WN, HEADS, BNB>(p, acc, smem, tid, bid, mt, nt, M, QQ, ph);
+    gemm_epilogue<T, BM, BN, WN, HEADS, BNB, RES>(p, acc, smem, tid, bid, mt, nt, M, QQ, ph);
 }
 
 // -------------------------------------------------------------------------------------
@@ -1057,7 +1129,7 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_ring_kernel(GemmParams p) {
 // 2 (NB2), P3 own A rows 0..63 (2), P4 own A rows 64..127 (2); counted waits: end of L4 vmcnt(4)
 // (both B parts of t+1 landed), end of C4 vmcnt(2) (A rows 0..63), end of C2 vmcnt(2+NB2) (A rows
 // 64..127 of stage t).  Every region is rewritten >= 3 phases after its last fragment read.
-template <int BN, bool HEADS, bool BNB = false>
+template <int BN, bool HEADS, bool BNB = false, bool RES = false>
 __global__ __launch_bounds__(512, 1) void conv_gemm_pp_kernel(GemmParams p) {
     typedef h16 T;
     constexpr int BM = 256, BK = 64, EPC = 8;
@@ -1354,15 +1426,41 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_pp_kernel(GemmParams p) {
             ypf[it] = bload(yrs, sel_off(ok, off));
         }
     }
+    // RES (scd_conv_gemm_res): byte offset of channel 0 of the residual at each of the lane's 8 pixels (-1 past M);
+    // the residual is read in the accumulator layout (8 B per fragment, buffer loads with no branch around them) and
+    // added in fp32 before the ReLU and the rounding
+    int rbase[RES ? 8 : 1];
+    __amdgpu_buffer_rsrc_t rrs = xrs;
+    if constexpr (RES) {
+        rrs = __builtin_amdgcn_make_buffer_rsrc((void*)p.res, (short)0, p.ybytes, 0x00020000);
+#pragma unroll
+        for (int a = 0; a < 8; ++a) {
+            const int m = mt * BM + 128 * grp + a * 16 + l16;
+            const bool ok = m < M;
+            const PixPos q = pix_of(ok ? m : 0);
+            rbase[a] = ok ? (int)out_off(q, 0) * (int)sizeof(T) : -1;
+        }
+    }
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
 #pragma unroll
         for (int a = 0; a < 8; ++a) {
             const int m = mt * BM + 128 * grp + a * 16 + l16;
             float v[4];
+            float rv[4] = {0.f, 0.f, 0.f, 0.f};
+            if constexpr (RES) {
+                const int col0 = nt * BN + wc * WCOLS + b * 16 + lg * 4;
+                const bool ok = rbase[a] >= 0 && col0 < p.Co;
+                const uint2 raw = __builtin_bit_cast(
+                    uint2, __builtin_amdgcn_raw_buffer_load_b64(rrs, sel_off(ok, rbase[a] + col0 * (int)sizeof(T)), 0, 0));
+                const unsigned rw[2] = {raw.x, raw.y};
+#pragma unroll
+                for (int r = 0; r < 4; ++r) rv[r] = h16_word_half(rw[r >> 1], r & 1);
+            }
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 v[r] = acc[a][b][r] + bias[b][r];
+                if constexpr (RES) v[r] += rv[r];
                 if (p.relu) v[r] = fmaxf(v[r], 0.f);
             }
             if constexpr (!BNB) {
@@ -3240,6 +3338,18 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* ws, int 
 
 template <typename T, int BM, int BN>
 int launch_gemm(GemmParams& p, int Mtot_tiles, hipStream_t st, int ks = 1) {
+    if (p.res) {
+        // scd_conv_gemm_res: no heads, no BN-backward sums
+        if (p.head_on || p.bnbwd) return SCD_ERR_ARG;
+        if constexpr (sizeof(T) == 2 && BM == 128 && BN == 128) {
+            if (ks == 2) {
+                hipLaunchKernelGGL((conv_gemm_kernel<T, BM, BN, false, false, 2, true>), dim3(Mtot_tiles), dim3(512), 0, st, p);
+                SCD_RETURN_LAUNCH();
+            }
+        }
+        hipLaunchKernelGGL((conv_gemm_kernel<T, BM, BN, false, false, 1, true>), dim3(Mtot_tiles), dim3(256), 0, st, p);
+        SCD_RETURN_LAUNCH();
+    }
     if constexpr (sizeof(T) == 2 && BM == 128 && BN == 128) {
         if (ks == 2 && !p.head_on) {
             if (p.bnbwd) hipLaunchKernelGGL((conv_gemm_kernel<T, BM, BN, false, true, 2>), dim3(Mtot_tiles), dim3(512), 0, st, p);
@@ -3276,7 +3386,11 @@ int launch_gemm(GemmParams& p, int Mtot_tiles, hipStream_t st, int ks = 1) {
 // weights as the A operand), so the outputs are the same bits.  Epilogue: channel blocks paired with
 // v_permlane16_swap (a lane then holds 8 consecutive channels of one pixel: 16-B stores); MODE 0 stores (+ forward BN
 // sums of the fp32 values when p.stats), 1 accumulates as the staged epilogues do (round(round(acc) + old)), 2 adds
-// the following BN+ReLU layer's backward sums (scd_conv_gemm_bnbwd: dz = stored gradient where y*rsc + rsh > 0).
+// the following BN+ReLU layer's backward sums (scd_conv_gemm_bnbwd: dz = stored gradient where y*rsc + rsh > 0), 3
+// (scd_conv_gemm_res) adds the bias (kept in LDS) and the residual to the fp32 accumulators, applies the ReLU and rounds
+// once: the residual is loaded like mode 1's old output (buffer loads; a NULL residual is a zero-length buffer, so
+// the loads return zeros and fetch nothing) and taken back from the store layout to the accumulator layout by the
+// same v_permlane16_swap (its own inverse); sum order as the shared epilogue's, so the outputs are its bits.
 // The sums (64 channels per wave): per-lane partials over the run, 16-lane DPP sums, the waves' partials in a fixed
 // order, one fp64 replica add per channel and workgroup.
 // The LDS plan of an instance.  SPL > 1 (STG): the SPL waves on the same pixels would each load the unit's operand as
@@ -3286,7 +3400,7 @@ int launch_gemm(GemmParams& p, int Mtot_tiles, hipStream_t st, int ks = 1) {
 template <int K, int N, int MODE, int SPL, int UA, int WV>
 struct S1x1Plan {
     static constexpr int WBYTES = N * K * 2;
-    static constexpr int PBYTES = MODE == 2 ? 4 * N * 4 : 0;       // BN parameters (mean, invstd, relu scale / shift)
+    static constexpr int PBYTES = MODE == 2 ? 4 * N * 4 : (MODE == 3 ? N * 4 : 0);   // BN parameters (mean, invstd, relu scale / shift); mode 3: the bias
     static constexpr int XU = 16 * UA * K * 2;                     // bytes of one pixel wave's unit
     static constexpr int XALL = 2 * (WV / SPL) * XU;               // two buffers per pixel wave
     static constexpr int OCC0 = 163840 / (WBYTES + PBYTES), OCC1 = 163840 / (WBYTES + PBYTES + XALL);
@@ -3306,7 +3420,7 @@ __global__ __launch_bounds__(64 * WV, 8 / WV) void conv1x1_stream_kernel(GemmPar
     constexpr int PXW = WV / SPL;                           // waves on different pixels
     constexpr int UP = 16 * UA;                             // pixels per unit (UA 16-pixel blocks)
     constexpr int XM = (K / 8 >= 16 ? 16 : K / 8) - 1;      // LDS swizzle: chunk c of row r at c ^ (r & XM)
-    constexpr bool SUMS = NH == 64 && MODE != 1;
+    constexpr bool SUMS = NH == 64 && MODE != 1 && MODE != 3;
     constexpr int NS = SUMS ? 4 * NB : 1;                   // per-lane channel slots of the sums
     constexpr int WBYTES = Plan::WBYTES, PBYTES = Plan::PBYTES, XU = Plan::XU, XBYTES = Plan::XBYTES;
     constexpr bool STG = Plan::STG;
@@ -3334,6 +3448,11 @@ __global__ __launch_bounds__(64 * WV, 8 / WV) void conv1x1_stream_kernel(GemmPar
             bnp[3 * N + i] = p.bn_rsh[cb + i];
         }
     }
+    if constexpr (MODE == 3) {
+        for (int i = tid; i < N; i += NT) bnp[i] = p.bias ? p.bias[cb + i] : 0.f;
+    }
+    const __amdgpu_buffer_rsrc_t ers = __builtin_amdgcn_make_buffer_rsrc(
+        (void*)(MODE == 3 && p.res ? p.res : p.x), (short)0, MODE == 3 && p.res ? p.ybytes : 0, 0x00020000);
     __syncthreads();
 
     const long chunk0 = (long)blockIdx.x * cpw;
@@ -3380,7 +3499,18 @@ __global__ __launch_bounds__(64 * WV, 8 / WV) void conv1x1_stream_kernel(GemmPar
             const char* src = MODE == 1 ? (const char*)p.y : p.bny;
 #pragma unroll
             for (int a = 0; a < UA; ++a) {
-                if constexpr (EPI_FR) {
+                if constexpr (MODE == 3 && EPI_FR) {
+                    const int o0 = (int)(((pix0(u) + 16 * a + (l16 & 7)) * ldy + cb + c0w + fr_cw) * 2);
+#pragma unroll
+                    for (int q = 0; q < NB / 4; ++q) {
+                        ev[a][2 * q] = bload(ers, o0 + 128 * q);
+                        ev[a][2 * q + 1] = bload(ers, o0 + 128 * q + 16 * ldy);
+                    }
+                } else if constexpr (MODE == 3) {
+#pragma unroll
+                    for (int pb = 0; pb < NB / 2; ++pb)
+                        ev[a][pb] = bload(ers, (int)(((pix0(u) + 16 * a + l16) * ldy + cb + 32 * pb + cst) * 2));
+                } else if constexpr (EPI_FR) {
                     // whole 128-B row pieces, in the stores' layout (turned into the fragment layout where used)
                     const char* r0 = src + ((pix0(u) + 16 * a + (l16 & 7)) * ldy + cb + c0w + fr_cw) * 2;
 #pragma unroll
@@ -3449,8 +3579,27 @@ __global__ __launch_bounds__(64 * WV, 8 / WV) void conv1x1_stream_kernel(GemmPar
             const int pb = 2 * q + j;
             const long m = pix0(u) + 16 * a + l16;
             hv4 h0, h1;
+            if constexpr (MODE == 3) {
+                // the residual from the store layout back to the two channel blocks' accumulator layout
+                const auto t0 = __builtin_amdgcn_permlane16_swap(evv[j].x, evv[j].z, false, false);
+                const auto t1 = __builtin_amdgcn_permlane16_swap(evv[j].y, evv[j].w, false, false);
+                const unsigned rx[2] = {t0[0], t1[0]}, ry[2] = {t0[1], t1[1]};
+                const float4 f0 = *(const float4*)(bnp + c0w + 32 * pb + 4 * lg);
+                const float4 f1 = *(const float4*)(bnp + c0w + 32 * pb + 16 + 4 * lg);
+                const float b0[4] = {f0.x, f0.y, f0.z, f0.w}, b1[4] = {f1.x, f1.y, f1.z, f1.w};
 #pragma unroll
-            for (int i = 0; i < 4; ++i) { h0[i] = (T)acc[a][2 * pb][i]; h1[i] = (T)acc[a][2 * pb + 1][i]; }
+                for (int i = 0; i < 4; ++i) {
+                    float v0 = acc[a][2 * pb][i] + b0[i], v1 = acc[a][2 * pb + 1][i] + b1[i];
+                    v0 += h16_word_half(rx[i >> 1], i & 1);
+                    v1 += h16_word_half(ry[i >> 1], i & 1);
+                    if (p.relu) { v0 = fmaxf(v0, 0.f); v1 = fmaxf(v1, 0.f); }
+                    h0[i] = (T)v0;
+                    h1[i] = (T)v1;
+                }
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) { h0[i] = (T)acc[a][2 * pb][i]; h1[i] = (T)acc[a][2 * pb + 1][i]; }
+            }
             const u32x2 x = __builtin_bit_cast(u32x2, h0), y = __builtin_bit_cast(u32x2, h1);
             const auto s0 = __builtin_amdgcn_permlane16_swap(x[0], y[0], false, false);
             const auto s1 = __builtin_amdgcn_permlane16_swap(x[1], y[1], false, false);
@@ -3612,7 +3761,10 @@ static int num_cus();
 static int launch_stream1x1(int dtype, GemmParams& p, int nphase, const scd_gemm_phase* phases, long Mtot,
                             hipStream_t st) {
     if (dtype != SCD_DT_BF16 || stream1x1_mode() == 0) return -1;
-    if (nphase != 1 || p.is != 1 || p.os != 1 || p.head_on || p.bias || p.relu || p.shuf) return -1;
+    // scd_conv_gemm_res: the bias / residual / ReLU mode (3), forward shapes without sums
+    const bool res3 = p.resmode && (p.bias || p.relu || p.res);
+    if (res3 && (p.stats || p.accumulate || p.bnbwd)) return -1;
+    if (nphase != 1 || p.is != 1 || p.os != 1 || p.head_on || p.shuf || (!res3 && (p.bias || p.relu || p.res))) return -1;
     const scd_gemm_phase& ph = phases[0];
     if (ph.ntaps != 1 || ph.dh[0] || ph.dw[0] || ph.wt[0] || ph.rho_h || ph.rho_w || ph.Qh != p.Ho || ph.Qw != p.Wo ||
         p.Hi != p.Ho || p.Wi != p.Wo || p.wrow != p.Ci)
@@ -3620,11 +3772,12 @@ static int launch_stream1x1(int dtype, GemmParams& p, int nphase, const scd_gemm
     const int K = p.Ci, N = p.Co;
     if (Mtot % 128 || Mtot < 65536 || Mtot * (long)(K > N ? K : N) >= (1L << 30)) return -1;
     p.xbytes = (int)(Mtot * K * 2);                          // the operand's buffer range (LDS-DMA path)
+    if (res3) p.ybytes = (int)(Mtot * N * 2);                // the residual's
     const bool sums = p.stats != nullptr;                    // forward statistics or BN-backward sums
     if (p.accumulate && sums) return -1;
     const long nchunks = Mtot / 128;
     const long cus = num_cus();
-    const int mode = p.bnbwd ? 2 : (p.accumulate ? 1 : 0);
+    const int mode = p.bnbwd ? 2 : (p.accumulate ? 1 : (res3 ? 3 : 0));
     // the whole N in one workgroup where an instance holds it, else slices of 256 output channels (grid.y; every
     // slice re-reads the operand, from L2 when the slices of a chunk run together)
     for (int attempt = 0; attempt < 2; ++attempt) {
@@ -3665,6 +3818,7 @@ static int launch_stream1x1(int dtype, GemmParams& p, int nphase, const scd_gemm
     SCD_S1X1(64, 64, 0, 1) SCD_S1X1(64, 64, 1, 1) SCD_S1X1(64, 64, 2, 1)
     SCD_S1X1(128, 64, 0, 1) SCD_S1X1(128, 64, 1, 1) SCD_S1X1(128, 64, 2, 1)
     SCD_S1X1(256, 64, 0, 1) SCD_S1X1(256, 64, 1, 1) SCD_S1X1(256, 64, 2, 1)
+    SCD_S1X1(64, 64, 3, 1) SCD_S1X1(128, 64, 3, 1) SCD_S1X1(256, 64, 3, 1)
     // K x N = 64 K elements (128-KB weight buffer): one workgroup of 8 waves per CU
 #define SCD_S1X1W(KK, NN, MM, SS, UU)                                                                                \
     if (K == KK && Nd == NN && mode == MM) {                                                                         \
@@ -3679,6 +3833,9 @@ static int launch_stream1x1(int dtype, GemmParams& p, int nphase, const scd_gemm
     } else {
         SCD_S1X1W(512, 128, 0, 1, 1) SCD_S1X1W(512, 128, 1, 1, 1) SCD_S1X1W(128, 512, 0, 2, 1)
         SCD_S1X1W(128, 512, 1, 2, 1) SCD_S1X1W(256, 256, 0, 1, 1) SCD_S1X1W(256, 256, 1, 1, 1)
+        // mode 3 (scd_conv_gemm_res): not (256, 256) and (128, 256), whose whole-width waves spill with the residual
+        // operand (148 / 124 B per lane): those shapes stay on the tiled kernels
+        SCD_S1X1W(512, 128, 3, 1, 1) SCD_S1X1W(128, 512, 3, 2, 1)
     }
 #undef SCD_S1X1W
     if (sums) {
@@ -3689,6 +3846,7 @@ static int launch_stream1x1(int dtype, GemmParams& p, int nphase, const scd_gemm
         SCD_S1X1(64, 256, 0, 1) SCD_S1X1(64, 256, 1, 1) SCD_S1X1(128, 256, 0, 1)
         SCD_S1X1(64, 128, 0, 1) SCD_S1X1(64, 128, 1, 1) SCD_S1X1(128, 128, 0, 1) SCD_S1X1(128, 128, 1, 1)
         SCD_S1X1(256, 128, 0, 1) SCD_S1X1(256, 128, 1, 1)
+        SCD_S1X1(64, 256, 3, 1) SCD_S1X1(64, 128, 3, 1) SCD_S1X1(128, 128, 3, 1) SCD_S1X1(256, 128, 3, 1)
     }
 #undef SCD_S1X1
     }
@@ -3842,7 +4000,7 @@ static int conv_gemm_launch(int dtype, GemmParams& p, int nphase, const scd_gemm
     {
         // two 256 x 128 workgroups per CU (conv_gemm_duo_kernel) where the grid gives each CU >= 2 tiles
         const int dm = duo_mode();
-        const bool shape = dtype == SCD_DT_BF16 && !p.head_on && p.Co % 128 == 0 &&
+        const bool shape = dtype == SCD_DT_BF16 && !p.head_on && !p.res && p.Co % 128 == 0 &&
                            (dm == 4 ? !pp_bn(dtype, p.Co) : (pp_bn(dtype, p.Co) || dm >= 2));
         const long dtiles = (long)cdiv(Mtot, 256) * (p.Co / 128);
         const bool take = dm == 3 ? (p.bnbwd && dtiles >= 16L * num_cus()) : dtiles >= 2L * num_cus();
@@ -3889,7 +4047,7 @@ static int conv_gemm_launch(int dtype, GemmParams& p, int nphase, const scd_gemm
             if (xb >= (1L << 31) - 64 || wb >= (1L << 31) - 64) return SCD_ERR_ARG;
             p.xbytes = (int)xb;
             p.wbytes = (int)wb;
-            const long yb = p.bnbwd ? (long)p.N * p.Ho * p.Wo * p.Co * esz : 0;
+            const long yb = (p.bnbwd || p.res) ? (long)p.N * p.Ho * p.Wo * p.Co * esz : 0;
             if (yb >= (1L << 31) - 64) return SCD_ERR_ARG;
             p.ybytes = (int)yb;
             hipStream_t st = (hipStream_t)stream;
@@ -3905,6 +4063,9 @@ static int conv_gemm_launch(int dtype, GemmParams& p, int nphase, const scd_gemm
             } else if (p.bnbwd) {
                 if (bn == 256) hipLaunchKernelGGL((conv_gemm_pp_kernel<256, false, true>), dim3(tiles), dim3(512), 0, st, p);
                 else hipLaunchKernelGGL((conv_gemm_pp_kernel<192, false, true>), dim3(tiles), dim3(512), 0, st, p);
+            } else if (p.res) {
+                if (bn == 256) hipLaunchKernelGGL((conv_gemm_pp_kernel<256, false, false, true>), dim3(tiles), dim3(512), 0, st, p);
+                else hipLaunchKernelGGL((conv_gemm_pp_kernel<192, false, false, true>), dim3(tiles), dim3(512), 0, st, p);
             } else {
                 if (bn == 256) hipLaunchKernelGGL((conv_gemm_pp_kernel<256, false>), dim3(tiles), dim3(512), 0, st, p);
                 else hipLaunchKernelGGL((conv_gemm_pp_kernel<192, false>), dim3(tiles), dim3(512), 0, st, p);
@@ -3916,7 +4077,10 @@ static int conv_gemm_launch(int dtype, GemmParams& p, int nphase, const scd_gemm
     {
         // 3x3 / s1 / p1, 64 -> 64 channels on whole rows of 64, 128 or 256 pixels: the persistent row-ring kernel
         const int flip = halo64_taps(p, nphase, phases);
-        if (dtype == SCD_DT_BF16 && flip >= 0 && halo64_mode() && !p.bias && !p.relu) {
+        // scd_conv_gemm_res: its forward variant with the bias / residual / ReLU epilogue
+        const bool l1res = p.resmode && (p.bias || p.relu || p.res);
+        if (dtype == SCD_DT_BF16 && flip >= 0 && halo64_mode() &&
+            (l1res ? (flip == 0 && !p.stats && !p.accumulate && !p.bnbwd) : (!p.bias && !p.relu && !p.res))) {
             if (p.Wo == 256 && p.bnbwd) return SCD_ERR_ARG;    // scd_conv_gemm_bnbwd: this kernel + separate reduce
             p.ntn = 1;
             p.ph[0] = phases[0];
@@ -3925,6 +4089,9 @@ static int conv_gemm_launch(int dtype, GemmParams& p, int nphase, const scd_gemm
             if (xb >= (1L << 31) - 64 || wb >= (1L << 31) - 64) return SCD_ERR_ARG;
             p.xbytes = (int)xb;
             p.wbytes = (int)wb;
+            const long yb = l1res ? (long)p.N * p.Ho * p.Wo * p.Co * esz : 0;
+            if (yb >= (1L << 31) - 64) return SCD_ERR_ARG;
+            p.ybytes = (int)yb;
             const int tiles = (int)(Mtot / 256);
             hipStream_t st = (hipStream_t)stream;
             // `run` tiles per workgroup down one image (about one workgroup per CU)
@@ -3934,7 +4101,9 @@ static int conv_gemm_launch(int dtype, GemmParams& p, int nphase, const scd_gemm
             const int grid = tiles / run;
 #define SCD_L1P_LAUNCH(WO)                                                                                              \
     do {                                                                                                                 \
-        if (WO != 256 && p.bnbwd) {                                                                                      \
+        if (l1res) {                                                                                                     \
+            hipLaunchKernelGGL((conv_gemm_l1p_kernel<WO, false, false, true>), dim3(grid), dim3(512), 0, st, p, run);    \
+        } else if (WO != 256 && p.bnbwd) {                                                                                      \
             if (flip) hipLaunchKernelGGL((conv_gemm_l1p_kernel<WO, true, WO != 256>), dim3(grid), dim3(512), 0, st, p, run); \
             else hipLaunchKernelGGL((conv_gemm_l1p_kernel<WO, false, WO != 256>), dim3(grid), dim3(512), 0, st, p, run);    \
         } else {                                                                                                         \
@@ -3980,6 +4149,7 @@ static int conv_gemm_launch(int dtype, GemmParams& p, int nphase, const scd_gemm
     if (ring) {
         if (p.head_on) hipLaunchKernelGGL((conv_gemm_ring_kernel<true>), dim3(tiles), dim3(512), 0, st, p);
         else if (p.bnbwd) hipLaunchKernelGGL((conv_gemm_ring_kernel<false, true>), dim3(tiles), dim3(512), 0, st, p);
+        else if (p.res) hipLaunchKernelGGL((conv_gemm_ring_kernel<false, false, true>), dim3(tiles), dim3(512), 0, st, p);
         else hipLaunchKernelGGL((conv_gemm_ring_kernel<false>), dim3(tiles), dim3(512), 0, st, p);
         SCD_RETURN_LAUNCH();
     }
@@ -4012,6 +4182,7 @@ static void fill_params(GemmParams& p, const void* x, const void* w, void* y, co
     p.shuf = 0;
     p.stamps = scd_calib_stamp_buffer;
     p.duo_ncu = 0; p.duo_delay = 0;
+    p.res = nullptr; p.resmode = 0;
     {
         // read per call (tests switch them to compare the variants)
         const char* e = getenv("SCD_HEADS_SERP");
@@ -4033,6 +4204,23 @@ extern "C" int scd_conv_gemm(int dtype, const void* x, const void* w, void* y, c
                 accumulate, nphase, phases, stream);
     GemmParams p;
     fill_params(p, x, w, y, bias, stats, N, Hi, Wi, Ci, Ho, Wo, Co, in_stride, out_stride, wrow, relu, accumulate);
+    return conv_gemm_launch(dtype, p, nphase, phases, stream);
+}
+
+// y = act(acc + bias + res): the folded-BatchNorm inference conv (scdhip/infer.py).  The residual joins the unrounded
+// fp32 accumulator before the ReLU and the result is rounded once at the store (the RES instantiations of the
+// register-staged, ring and ping-pong kernels; `accumulate` adds after the ReLU and a first rounding).  res == NULL
+// runs the very kernels of scd_conv_gemm.  The row-ring kernel (forward) and the 1x1 stream kernel (mode 3) have the
+// epilogue too and take this entry point's calls with a bias, a ReLU or a residual; the duo and heads kernels do not.
+extern "C" int scd_conv_gemm_res(int dtype, const void* x, const void* w, void* y, const float* bias, const void* res,
+                                 int N, int Hi, int Wi, int Ci, int Ho, int Wo, int Co, int in_stride, int out_stride,
+                                 int wrow, int relu, int nphase, const scd_gemm_phase* phases, void* stream) {
+    SCD_F16_FWD(scd_conv_gemm_res, x, w, y, bias, res, N, Hi, Wi, Ci, Ho, Wo, Co, in_stride, out_stride, wrow, relu,
+                nphase, phases, stream);
+    if (res && res == y) return SCD_ERR_ARG;
+    GemmParams p;
+    fill_params(p, x, w, y, bias, nullptr, N, Hi, Wi, Ci, Ho, Wo, Co, in_stride, out_stride, wrow, relu, 0);
+    p.res = (const char*)res; p.resmode = 1;
     return conv_gemm_launch(dtype, p, nphase, phases, stream);
 }
 

@@ -14,6 +14,7 @@
 #ifdef SCD_F16_BUILD
 #define scd_conv_gemm scd_conv_gemm__f16
 #define scd_conv_gemm_bnbwd scd_conv_gemm_bnbwd__f16
+#define scd_conv_gemm_res scd_conv_gemm_res__f16
 #define scd_conv_gemm_heads scd_conv_gemm_heads__f16
 #define scd_conv_gemm_heads_keep scd_conv_gemm_heads_keep__f16
 #define scd_conv_wgrad_workspace scd_conv_wgrad_workspace__f16
@@ -79,6 +80,7 @@
 #define SCD_F16_DECL(fn) extern "C" decltype(fn) fn##__f16;
 SCD_F16_DECL(scd_conv_gemm)
 SCD_F16_DECL(scd_conv_gemm_bnbwd)
+SCD_F16_DECL(scd_conv_gemm_res)
 SCD_F16_DECL(scd_conv_gemm_heads)
 SCD_F16_DECL(scd_conv_gemm_heads_keep)
 SCD_F16_DECL(scd_conv_wgrad_nsplit2)

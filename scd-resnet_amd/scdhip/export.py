@@ -17,7 +17,7 @@ import torch
 _LIB = torch.library.Library("scd", "DEF")
 _LIB.define("centernet_decode(Tensor x, Tensor[] tensors, str arch, str mode, str dtype) -> Tensor")
 
-_MODELS = {}        # (arch, mode, dtype, device) -> (Wrapper, tensor list it was bound to)
+_MODELS = {}        # (arch, mode, dtype, device) -> [Wrapper, key of the tensor list it was bound to, plugin model]
 _DTYPES = {"bf16": torch.bfloat16, "fp16": torch.float16, "fp32": torch.float32}
 
 
@@ -34,18 +34,22 @@ def _wrapper_for(arch, mode, dtype, device):
         m = _plugin_model(arch).to(device)
         m.set_compute_dtype(_DTYPES[dtype])
         m.train(mode == "train")
-        hit = [wrappers.Wrapper(m), None]
+        # mode "fold": the Wrapper goes around scdhip.infer.fold(m) once the op's tensors are bound (_decode_impl)
+        hit = [wrappers.Wrapper(m) if mode != "fold" else None, None, m]
         _MODELS[key] = hit
     return hit
 
 
 def _decode_impl(x, tensors, arch, mode, dtype):
     hit = _wrapper_for(arch, mode, dtype, x.device)
-    w = hit[0]
+    m = hit[2]
     ptrs = tuple(t.data_ptr() for t in tensors)
+    if mode == "fold":
+        # the folded operands are a snapshot: taken when the tensors are bound and again when any of them changes
+        ptrs += tuple(t._version for t in tensors)
     if hit[1] != ptrs:
         # bind the module's parameters and buffers to the op's tensors (views, no copy)
-        own = list(w.model.parameters()) + list(w.model.buffers())
+        own = list(m.parameters()) + list(m.buffers())
         if len(own) != len(tensors):
             raise RuntimeError("scd::centernet_decode: %d tensors for a %s model with %d" % (len(tensors), arch,
                                                                                           len(own)))
@@ -53,9 +57,16 @@ def _decode_impl(x, tensors, arch, mode, dtype):
             if o.shape != t.shape:
                 raise RuntimeError("scd::centernet_decode: tensor shape %s for %s" % (tuple(t.shape), tuple(o.shape)))
             o.data = t.to(device=x.device, dtype=o.dtype)
+        if mode == "fold":
+            if hit[0] is None:
+                from . import infer
+                wrappers = importlib.import_module("trainer.wrappers.centerOffsetResidual")
+                hit[0] = wrappers.Wrapper(infer.fold(m))
+            else:
+                hit[0].model.refold()
         hit[1] = ptrs
     with torch.no_grad():
-        return w(x)
+        return hit[0](x)
 
 
 _LIB.impl("centernet_decode", _decode_impl, "CUDA")
@@ -78,7 +89,9 @@ class Traceable(torch.nn.Module):
 def trace(arch, model, example, path, mode="train", dtype="bf16"):
     """torch.jit.trace of the decoded forward (trace.py:58-66); writes `path`, returns the traced module.  `mode`:
     "train" keeps BatchNorm on batch statistics, as the reference's trace of an un-eval'ed model does; "eval"
-    uses the running statistics."""
+    uses the running statistics; "fold" runs the running statistics folded into the conv operands
+    (scdhip.infer).  The archive carries the unfolded parameters and buffers in every mode, so files stay
+    interchangeable; folding happens when the op binds them."""
     t = Traceable(arch, model, mode, dtype).to(example.device)
     traced = torch.jit.trace(t, example, check_trace=False)
     traced.save(path)
@@ -108,4 +121,7 @@ def load(path, arch=None, device=None, mode="train", dtype="bf16"):
     m = m.to(device).set_compute_dtype(_DTYPES[dtype])
     m.train(mode == "train")
     wrappers = importlib.import_module("trainer.wrappers.centerOffsetResidual")
+    if mode == "fold":
+        from . import infer
+        m = infer.fold(m)
     return wrappers.Wrapper(m)

@@ -702,6 +702,45 @@ def conv_fwd(x, wpack, Co, kh, kw, stride, pad, bias=None, stats=None, relu=Fals
     return _gemm(x, wpack, out, Co, Ho, Wo, stride, 1, _fwd_phase(kh, kw, pad, Ho, Wo), bias, stats, relu)
 
 
+def gemm_res(x, wpack, y, Co, Ho, Wo, in_stride, out_stride, phases, bias=None, res=None, relu=False):
+    """scd_conv_gemm_res: y = act(gather-GEMM + bias + res), the sum in fp32 and one rounding at the store (the
+    folded-BatchNorm inference conv, scdhip.infer).  res: NHWC (N,Ho,Wo,Co) in x's dtype, or None."""
+    _need_gpu(x)
+    N, Hi, Wi, Ci = x.shape
+    if Ci % (64 if x.dtype in HALF else 32):
+        raise RuntimeError("scd_conv_gemm_res: %d input channels (a multiple of the K stage is required)" % Ci)
+    if res is not None and (res.shape != y.shape or res.dtype != y.dtype or not res.is_contiguous()):
+        raise RuntimeError("scd_conv_gemm_res: the residual must be a contiguous NHWC tensor of the output's shape "
+                           "and dtype")
+    t0 = ClassTimer.begin()
+    L.call("scd_conv_gemm_res", dt(x), ptr(x), ptr(wpack), ptr(y), ptr(bias), ptr(res), N, Hi, Wi, Ci, Ho, Wo, Co,
+           in_stride, out_stride, wpack.shape[1], int(relu), phases.n, phases.arr, stream())
+    if t0 is not None:
+        ClassTimer.end("gemm", t0, _gemm_flops(Ci, Co, N, phases))
+    return y
+
+
+def conv_fwd_res(x, wpack, Co, kh, kw, stride, pad, bias=None, res=None, relu=False, out=None):
+    """Conv2d forward (NHWC) with the fp32 bias / residual / ReLU epilogue; wpack = pack_weight(w, mode=0)."""
+    N, H, W, _ = x.shape
+    Ho = (H + 2 * pad - kh) // stride + 1
+    Wo = (W + 2 * pad - kw) // stride + 1
+    if out is None:
+        out = torch.empty(N, Ho, Wo, Co, dtype=x.dtype, device=x.device)
+    return gemm_res(_c(x), wpack, out, Co, Ho, Wo, stride, 1, _fwd_phase(kh, kw, pad, Ho, Wo), bias, res, relu)
+
+
+def deconv_fwd_res(x, wpack_t, Cout, k=4, stride=2, pad=1, bias=None, res=None, relu=False):
+    """ConvTranspose2d(k, stride, pad, output_padding=0) forward with the fp32 bias / residual / ReLU epilogue;
+    wpack_t = pack_weight(W_t, mode=1).  The sub-pixel phases are those of deconv_fwd."""
+    N, H, W, _ = x.shape
+    Ho = (H - 1) * stride - 2 * pad + k
+    Wo = (W - 1) * stride - 2 * pad + k
+    out = torch.empty(N, Ho, Wo, Cout, dtype=x.dtype, device=x.device)
+    return gemm_res(_c(x), wpack_t, out, Cout, Ho, Wo, 1, stride, _dgrad_phases(k, k, stride, pad, Ho, Wo), bias, res,
+                    relu)
+
+
 def conv_dgrad(dy, wpack_t, Cin, Hc, Wc, kh, kw, stride, pad, out=None, accumulate=False, stats=None, bn_bwd=None):
     """Input-gradient of Conv2d (NHWC) as a phase-decomposed gather-GEMM; wpack_t = pack_weight(w, mode=1).
     Also ConvTranspose2d forward (with the transposed conv's geometry).  bn_bwd: see _gemm."""

@@ -8,7 +8,8 @@ slide resized to whole strides by torch-'reflect' padding plus its opencv column
 Clip extraction + greyscale + normalisation run as scd_slide_tiles (nothing padded is materialised), the score
 threshold and the projection back to slide pixels as scd_slide_detections; the slide goes to the device once.
 
-CLI:  python slide.py <architecture> <state_dict.pt | traced.pt> <image> [<image> ...]   (-eval: BN in eval mode)
+CLI:  python slide.py <architecture> <state_dict.pt | traced.pt> <image> [<image> ...]   (-eval: BN in eval mode;
+      -fold: eval mode with BatchNorm folded into the conv operands, scdhip/infer.py)
 """
 import sys
 from math import ceil
@@ -73,8 +74,9 @@ def analyseImages(model, fullPath):
 
 def main(argv):
     import importlib
-    evalMode = "-eval" in argv
-    argv = [a for a in argv if a != "-eval"]
+    foldMode = "-fold" in argv
+    evalMode = "-eval" in argv or foldMode
+    argv = [a for a in argv if a not in ("-eval", "-fold")]
     if len(argv) < 3:
         print(__doc__)
         return 2
@@ -84,13 +86,16 @@ def main(argv):
         # a TorchScript archive (test.py:145 loads the trace.py output): ours replays scd::centernet_decode, a
         # reference trace has its weights moved into the plugin model (scdhip/export.py)
         from scdhip import export
-        wrapper = export.load(ckpt, arch=arch, mode="eval" if evalMode else "train")
+        wrapper = export.load(ckpt, arch=arch, mode="fold" if foldMode else ("eval" if evalMode else "train"))
     else:
         plugin = importlib.import_module("trainer.model." + arch)
         model = plugin.model(**plugin.modelParams)
         model.load_state_dict(torch.load(ckpt, map_location="cpu", weights_only=True))
         model = model.cuda()
         model.train(not evalMode)
+        if foldMode:
+            from scdhip import infer
+            model = infer.fold(model)
         wrapper = importlib.import_module("trainer.wrappers.centerOffsetResidual").Wrapper(model)
     for img in images:
         for d in analyseImages(wrapper, img):

@@ -1,13 +1,14 @@
 """trace.py -- TorchScript `.pt` of a trained model's decoded inference (trace.py of the reference, same arguments).
 
-python trace.py <output.pt> -a <architecture> -m <state_dict.pth> -s "1 1 512 512" [-gpu] [-wrapped] [-eval]
+python trace.py <output.pt> -a <architecture> -m <state_dict.pth> -s "1 1 512 512" [-gpu] [-wrapped] [-eval] [-fold]
         [-dtype bf16|fp16|fp32]
 
 The traced graph is one scd::centernet_decode call over the model's parameters and buffers (scdhip/export.py), so
 the `.pt` replays the libscdhip path after torch.jit.load in a process that imported scdhip.export (slide.py does).
 The model always runs on the GPU (-gpu is accepted for the reference's command lines); -wrapped strips the
 DataParallel `module.` prefix the reference adds; -eval traces BatchNorm on running statistics (the reference
-traces the model as constructed, i.e. on batch statistics).
+traces the model as constructed, i.e. on batch statistics); -fold implies -eval and replays with the running
+statistics folded into the conv operands (scdhip/infer.py; the archive still holds the unfolded tensors).
 """
 import argparse
 import os
@@ -29,6 +30,7 @@ def parseArguments(argv=None):
     parser.add_argument("-gpu", dest="useGPU", const=True, default=False, action="store_const")
     parser.add_argument("-wrapped", dest="isWrapped", const=True, default=False, action="store_const")
     parser.add_argument("-eval", dest="evalMode", const=True, default=False, action="store_const")
+    parser.add_argument("-fold", dest="foldMode", const=True, default=False, action="store_const")
     parser.add_argument("-dtype", dest="dtype", default="bf16", choices=["bf16", "fp16", "fp32"])
     return parser.parse_args(argv)
 
@@ -53,8 +55,8 @@ def begin(args):
     model = model.to(dev)
     shape = [int(s) for s in args.inputShape.split()]
     dummy = torch.rand(*shape, device=dev)
-    traced = export.trace(args.modelArchitecture, model, dummy, args.output, mode="eval" if args.evalMode else "train",
-                          dtype=args.dtype)
+    mode = "fold" if args.foldMode else ("eval" if args.evalMode else "train")
+    traced = export.trace(args.modelArchitecture, model, dummy, args.output, mode=mode, dtype=args.dtype)
     out = traced(dummy)
     Logger.log("The loaded models accepts Input in {} and Output in {}".format(tuple(dummy.shape), tuple(out.shape)))
     Logger.log("Output saved to {}".format(args.output))
