@@ -13,6 +13,7 @@
 #include <algorithm>
 #include <type_traits>
 
+#include "gemm_common.h"
 #include "scd_common.h"
 
 // Compile-time ablations of the LDS-DMA GEMM kernels (make ABLATE=N builds a separate library; never in the
@@ -22,21 +23,6 @@
 // its code (the waitcnt pass falls back to full drains around branched loads).
 #ifndef SCD_ABLATE
 #define SCD_ABLATE 0
-#endif
-#ifndef L1P_SWAP
-#define L1P_SWAP 1      // conv_gemm_l1p_kernel, 256-pixel rows: 16-B stores of channel-block pairs (A/B option)
-#endif
-#ifndef S1X1_FULLROW
-#define S1X1_FULLROW 1  // conv1x1_stream_kernel: stores of whole 128-B row pieces (A/B option)
-#endif
-#ifndef S1X1_STG
-#define S1X1_STG 1    // conv1x1_stream_kernel: waves that share pixels take the operand from one LDS-DMA copy (A/B option)
-#endif
-#ifndef S1X1_UA2
-#define S1X1_UA2 1    // conv1x1_stream_kernel: 32-pixel units where K = 64 (A/B build option)
-#endif
-#ifndef WGRAD_OCC
-#define WGRAD_OCC 2   // register-staged weight-gradient kernel: workgroups per CU the registers are budgeted for
 #endif
 
 extern unsigned long long* scd_calib_stamp_buffer;   // calib.hip (stamped diagnostic builds)
@@ -58,7 +44,8 @@ struct GemmParams {
     scd_gemm_phase ph[SCD_MAX_PHASES];
     // optional fused CenterNet head tails (n-tile t == head t, BN == head hidden width)
     int head_on;
-    int debug;      // ablation (SCD_GEMM_DEBUG): 1 = no MFMA, 2 = no DMA after the prologue
+    // heads384: K-stage order reversed on every other round of 256 workgroups (kserp = 1; SCD_HEADS_SERP)
+    int kserp;
     int head_od[4];
     const float* head_w[4];
     const float* head_b[4];
@@ -78,12 +65,8 @@ struct GemmParams {
     // scd_conv_dgrad_s2 (ping-pong kernel): GEMM column c = phase * Co/4 + channel is stored at output pixel
     // (2 oh + phase / 2, 2 ow + phase % 2) of a (2 Ho, 2 Wo, Co/4) tensor
     int shuf;
-    // heads384: K-stage order reversed on every other round of 256 workgroups (kserp = 1; SCD_HEADS_SERP)
-    int kserp;
     // stamped diagnostic build only (SCD_STAMP, calib.hip): per-workgroup main-loop clock stamps
     unsigned long long* stamps;
-    // duo kernel: workgroups [duo_ncu, 2 duo_ncu) sleep duo_delay x 8K cycles before their first tile
-    int duo_ncu, duo_delay;
     // scd_conv_gemm_res (RES instantiations): residual (N, Ho, Wo, Co) in the output's type, added to the fp32
     // accumulator + bias before the ReLU and the one rounding at the store; ybytes is its buffer range
     const char* res;
@@ -124,18 +107,9 @@ __device__ __forceinline__ f32x4 mfma_16x16x16(hx4 a, hx4 b, f32x4 c) {
 #endif
 }
 
-#ifndef PP_PRIO
-// ping-pong kernels (conv_gemm_pp, heads384, wgrad_pp2): 1 = s_setprio 1 around every MFMA segment (the round-1
-// form), 2 = static priority for the second-dispatched group for the whole main loop, no per-segment flips
-// (MI355X_MICROARCH.md "Two waves per SIMD" item 4), 0 = none (A/B build option)
-#define PP_PRIO 1
-#endif
-#ifndef PP_YPF
-#define PP_YPF 1      // ping-pong BN-backward epilogue: the pre-BN rows loaded before the accumulators are staged
-#endif
-#ifndef PP_DPP
-#define PP_DPP 1      // ping-pong epilogue: BN sums over the 16 pixel lanes with DPP row ops instead of ds_bpermute
-#endif
+// (The ping-pong kernels -- conv_gemm_pp, heads384, wgrad_pp2 -- set s_setprio 1 around every MFMA segment, the round-1
+// form; a static priority for the second-dispatched group for the whole main loop, MI355X_MICROARCH.md "Two waves per
+// SIMD" item 4, and none at all were A/B builds that did not replace it.)
 
 // sum over the 16 lanes of a DPP row (every lane gets it): quad butterflies, then the half-row and row mirrors
 __device__ __forceinline__ float row16_sum(float v) {
@@ -817,7 +791,7 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_l1p_kernel(GemmParams p, int
                     }
                 }
         }
-        if constexpr (DIRECT && L1P_SWAP) {
+        if constexpr (DIRECT) {
             // the tile is row r of image n: lane's pixel 64pw + 16a + l16 is its column.  The two channel blocks
             // paired by v_permlane16_swap: the lane then holds 8 consecutive channels 32chh + 4lg + 12(lg & 1) ..,
             // one 16-B store per pixel block (16 pixels x 64 B per instruction instead of 16 x 32 B)
@@ -846,25 +820,6 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_l1p_kernel(GemmParams p, int
                 }
                 *(uint4*)((T*)p.y + off) = v;
             }
-        } else if constexpr (DIRECT) {
-            // the tile is row r of image n: lane's pixel 64pw + 16a + l16 is its column; channels 32chh + 16b + 4lg
-            const long base = ((long)(n * p.Ho + r) * p.Wo) * 64;
-            typedef __attribute__((ext_vector_type(4))) h16 bf16x4;
-#pragma unroll
-            for (int b = 0; b < 2; ++b)
-#pragma unroll
-                for (int a = 0; a < 4; ++a) {
-                    const long off = base + (long)(64 * pw + 16 * a + l16) * 64 + 32 * chh + 16 * b + 4 * lg;
-                    bf16x4 o;
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) o[q] = (h16)acc[a][b][q];
-                    if (p.accumulate) {
-                        const bf16x4 old4 = *(const bf16x4*)((const T*)p.y + off);
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) o[q] = (h16)((float)o[q] + (float)old4[q]);
-                    }
-                    *(bf16x4*)((T*)p.y + off) = o;
-                }
         } else {
         // stage: lane holds pixel 64pw + 16a + l16, channels 32chh + 16b + 4lg + (0..3)
 #pragma unroll
@@ -1274,7 +1229,7 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_pp_kernel(GemmParams p) {
             }
             return;
         }
-        if constexpr (PP_PRIO == 1) __builtin_amdgcn_s_setprio(1);
+        __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int s = 0; s < 2; ++s)
 #pragma unroll
@@ -1282,10 +1237,10 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_pp_kernel(GemmParams p) {
 #pragma unroll
                 for (int b = 0; b < NB; ++b)
                     acc[2 * q + a][b] = mfma_16x16x32_h16(bfr[b][s], af[a][s], acc[2 * q + a][b]);
-        if constexpr (PP_PRIO == 1) __builtin_amdgcn_s_setprio(0);
+        __builtin_amdgcn_s_setprio(0);
         __builtin_amdgcn_sched_barrier(0);
     };
-    // ablations (SCD_GEMM_DEBUG): 3 = no DMA instructions in the loop, 4 = no fragment reads in the loop,
+    // ablations (SCD_ABLATE builds): 3 = no DMA instructions in the loop, 4 = no fragment reads in the loop,
     // 5 = no barriers in the loop, 60 = no output stores, 61 = no epilogue (timing only; 3-5, 60, 61 give wrong
     // results; tools/pp_probe.py)
     constexpr int dbg = SCD_ABLATE;
@@ -1308,7 +1263,6 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_pp_kernel(GemmParams p) {
         bar();
         if constexpr (dbg == 4) { read_b(smem); read_a(smem, 0, afx); read_a(smem, 1, afy); }
         if (grp == 1) bar();                 // stagger: group 1 runs one barrier behind
-        if constexpr (PP_PRIO == 2) { if (grp == 1) __builtin_amdgcn_s_setprio(1); }
         for (int t = 0; t < KT; ++t) {
             char* cur = smem + (t & 1) * STAGE;
             char* nxt = smem + ((t & 1) ^ 1) * STAGE;
@@ -1345,7 +1299,6 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_pp_kernel(GemmParams p) {
             bar();
         }
         if (grp == 0) bar();
-        if constexpr (PP_PRIO == 2) __builtin_amdgcn_s_setprio(0);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -1396,8 +1349,7 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_pp_kernel(GemmParams p) {
         return ((long)(q.n * p.Ho + oh) * p.Wo + ow) * p.Co + col;
     };
     // BN-backward mode (below): the lane's rows of the pre-BN activation are loaded now, in flight while the
-    // accumulators are staged (the fragment registers are free after the main loop); PP_YPF=0 loads them in the
-    // store loop
+    // accumulators are staged (the fragment registers are free after the main loop)
     float bias[NB][4];                                       // before the row loads (in-order returns)
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
@@ -1410,8 +1362,8 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_pp_kernel(GemmParams p) {
     const int rsub = lane / CPR, chx = lane - (lane / CPR) * CPR;
     // Buffer loads with no branch around them (rows past M / columns past Co take an out-of-range offset and read
     // zeros), so the compiler's wait for the bias loads above them stays a counted one
-    uint4 ypf[PP_YPF && BNB ? NIT : 1];
-    if constexpr (PP_YPF && BNB) {
+    uint4 ypf[BNB ? NIT : 1];
+    if constexpr (BNB) {
         const __amdgpu_buffer_rsrc_t yrs = __builtin_amdgcn_make_buffer_rsrc((void*)p.bny, (short)0, p.ybytes, 0x00020000);
         const int colb = nt * BN + wc * WCOLS + chx * EPC;
         const bool cok = rsub < RPI && colb < p.Co;
@@ -1525,8 +1477,7 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_pp_kernel(GemmParams p) {
                 }
                 float d8[EPC], y8[EPC];
                 Vec16<T>::load(&v, d8);
-                if constexpr (PP_YPF && BNB) Vec16<T>::load(&ypf[it], y8);
-                else Vec16<T>::load((const T*)p.bny + off, y8);
+                Vec16<T>::load(&ypf[it], y8);
                 // the sums on every row (+0 for rows masked off; they never hold -0) and only the store under the
                 // branch: the BN parameters are then waited for once, not on every row behind the previous store
 #pragma unroll
@@ -1598,14 +1549,8 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_pp_kernel(GemmParams p) {
             for (int b = 0; b < NB; ++b)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    float s = csum[b][r], q = csq[b][r];
-                    if constexpr (PP_DPP) {
-                        s = row16_sum(s);
-                        q = row16_sum(q);
-                    } else {
-#pragma unroll
-                        for (int o = 1; o < 16; o <<= 1) { s += __shfl_xor(s, o, 64); q += __shfl_xor(q, o, 64); }
-                    }
+                    // over the 16 pixel lanes with DPP row ops, not ds_bpermute
+                    const float s = row16_sum(csum[b][r]), q = row16_sum(csq[b][r]);
                     if (l16 == 0) {
                         const int c = wc * WCOLS + b * 16 + lg * 4 + r;
                         red[(grp * BN + c) * 2 + 0] = s;
@@ -1689,409 +1634,6 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_pp_kernel(GemmParams p) {
                     if (full) *dst = val;
                     else atomic_add_f32(dst, val);
                 }
-            }
-        }
-    }
-}
-
-// -------------------------------------------------------------------------------------
-// Two-workgroups-per-CU bf16 gather-GEMM ("duo", round 6).  The ping-pong kernel above holds a CU
-// alone (two 64-KiB stages, 8 waves x ~206 VGPRs), so nothing runs while its tile epilogue stores 128 KiB and (BN
-// backward) reads another 128 KiB: stamped in the step's shapes, the main loops take 53 % of the heatmap-head input
-// gradient and 76 % of the deconv3 one (profiles/r6_clock.txt), the rest is per-tile epilogue and prologue with the
-// matrix pipe idle.  Here a 256 x 128 tile belongs to a 4-wave workgroup (waves 2 x 2, 128 x 64 each: the
-// ping-pong kernel's per-wave tile, fragment reads per MFMA and epilogue), its LDS is a 3-slot ring of BK = 32
-// stages (rows of 64 B, 24 KiB per stage) that the epilogue reuses as its staging buffer, and its registers fit
-// 2 waves per SIMD -- so TWO workgroups share each CU, and one's epilogue runs beside the other's MFMAs.  The
-// workgroups of the first round's second slot (blockIdx in [CUs, 2 CUs)) start half a tile late (s_sleep), so the two
-// slots of a CU stay half a tile apart for the whole launch.
-// K order: (64-channel chunk, tap, 32-channel half), so both halves of a pixel's 128-B line are fetched in
-// consecutive K-steps, and every output sees the same MFMA sequence as the ping-pong kernel's (chunk, tap, s = half):
-// bit-identical results.
-// LDS row r (64 B, 4 chunks of 16 B): chunk c in slot c ^ F[(r >> 2) & 3], F = {0, 2, 3, 1}: the 16 lanes of every
-// ds_read_b128 lane group (rows l16, chunk lg) then hit 16 distinct 16-B units of the 256-B bank window; the DMA
-// writes a wave-instruction's 1 KiB lane-linearly (16 rows), so the swizzle is applied to the source chunk.
-// One barrier per K-step: wait for this wave's DMAs of stage k (vmcnt(6): stage k+1's 6 stay in flight), barrier,
-// issue stage k+2 into the slot stage k-1 used, read the fragments of stage k, 32 MFMAs.
-#ifndef DUO_PRIO
-#define DUO_PRIO 1    // duo kernel: s_setprio 1 around a K-step's MFMAs (A/B build option)
-#endif
-#ifndef DUO_ILV
-#define DUO_ILV 1     // duo kernel: DMA issues and fragment reads interleaved with the MFMAs (A/B build option)
-#endif
-__device__ __forceinline__ int duo_swz(int r) { return (0x78 >> (2 * ((r >> 2) & 3))) & 3; }
-
-__global__ __launch_bounds__(256, 2) void conv_gemm_duo_kernel(GemmParams p) {
-    typedef h16 T;
-    constexpr int BM = 256, BN = 128, BK = 32, EPC = 8;
-    constexpr int NB = 4, WCOLS = 64;            // per wave: 8 x 4 blocks of 16 x 16 (128 pixels x 64 channels)
-    constexpr int ROWB = BK * 2;                 // 64-B LDS rows
-    constexpr int STAGE = (BM + BN) * ROWB;      // 24 KiB
-    constexpr int NSLOT = 3;
-    constexpr int EROW = WCOLS * 2 + 16;         // epilogue staging row (144 B)
-    constexpr int EPI = 4 * 128 * EROW;          // 72 KiB = the ring
-    constexpr int RING = NSLOT * STAGE;
-    constexpr int SMEM = (RING > EPI ? RING : EPI) + 2 * BN * 2 * 4;    // + the BN partial sums [2][BN][2]
-    __shared__ __attribute__((aligned(16))) char smem[SMEM];
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave >> 1, wn = wave & 1;
-    int bid;
-    {
-        const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = blockIdx.x & 7;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (blockIdx.x >> 3);
-    }
-    // the first round's second workgroup per CU starts about half a tile late (host-sized, p.duo_delay x 8K cycles)
-    if ((int)blockIdx.x >= p.duo_ncu && (int)blockIdx.x < 2 * p.duo_ncu) {
-        for (int i = 0; i < p.duo_delay; ++i) __builtin_amdgcn_s_sleep(127);
-    }
-    int phase = 0;
-#pragma unroll
-    for (int i = 1; i < SCD_MAX_PHASES; ++i)
-        if (i < p.nphase && bid >= p.tile_start[i]) phase = i;
-    const scd_gemm_phase& ph = p.ph[phase];
-    const int local = bid - p.tile_start[phase];
-    const int mt = local / p.ntn;
-    const int nt = local - mt * p.ntn;
-    const int QQ = ph.Qh * ph.Qw;
-    const int M = p.N * QQ;
-
-    // DMA: lane -> row lr = lane / 4 of a 16-row piece, LDS slot lane & 3, source chunk (lane & 3) ^ F[lane / 16]
-    const int lr = lane >> 2;
-    const int cch = (lane & 3) ^ duo_swz(lr);
-    // A rows 64 * wave + 16 i + lr (i < 4): byte offset at tap (0, 0) of channel 0 + in-image tap mask
-    int a_base[4];
-    unsigned a_mask[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int m = mt * BM + 64 * wave + 16 * i + lr;
-        const bool ok = m < M;
-        const int mm = ok ? m : 0;
-        const int n = mm / QQ;
-        const int rem = mm - n * QQ;
-        const int qh = rem / ph.Qw;
-        const int qw = rem - qh * ph.Qw;
-        const int ih0 = p.is * qh, iw0 = p.is * qw;
-        a_base[i] = ((n * p.Hi + ih0) * p.Wi + iw0) * p.Ci * 2 + cch * 16;
-        unsigned msk = 0;
-        for (int t = 0; t < ph.ntaps; ++t) {
-            const int ih = ih0 + ph.dh[t], iw = iw0 + ph.dw[t];
-            if (ok && (unsigned)ih < (unsigned)p.Hi && (unsigned)iw < (unsigned)p.Wi) msk |= 1u << t;
-        }
-        a_mask[i] = msk;
-    }
-    // B rows 32 * wave + 16 j + lr (j < 2)
-    int b_base[2];
-    bool b_ok[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int nn = nt * BN + 32 * wave + 16 * j + lr;
-        b_ok[j] = nn < p.Co;
-        b_base[j] = (b_ok[j] ? nn : 0) * p.wrow * 2 + cch * 16;
-    }
-    const int KT = ph.ntaps * (p.Ci / 64) * 2;
-    const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, (short)0, p.xbytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, (short)0, p.wbytes, 0x00020000);
-
-    struct StageArgs { int live, tap, adelta, bdelta; };
-    auto stage_args = [&](int kt_req) {
-        StageArgs a;
-        a.live = kt_req < KT;
-        const int kt = min(kt_req, KT - 1);
-        const int h = kt & 1, k2 = kt >> 1;
-        const int chunk = k2 / ph.ntaps, tap = k2 - chunk * ph.ntaps;   // 64-channel chunk outer, tap, half inner
-        a.tap = tap;
-        a.adelta = ((ph.dh[tap] * p.Wi + ph.dw[tap]) * p.Ci + chunk * 64 + h * 32) * 2;
-        a.bdelta = (ph.wt[tap] * p.Ci + chunk * 64 + h * 32) * 2;
-        return a;
-    };
-    // the 6 DMA instructions of one K-step (always 6: the vmcnt counts are static)
-    auto issue = [&](const StageArgs& g, char* buf) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const bool ok = g.live && ((a_mask[i] >> g.tap) & 1u);
-            dma16(xrs, buf + (64 * wave + 16 * i) * ROWB, sel_off(ok, a_base[i] + g.adelta));
-        }
-        char* Bs = buf + BM * ROWB;
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-            dma16(wrs, Bs + (32 * wave + 16 * j) * ROWB, sel_off(g.live && b_ok[j], b_base[j] + g.bdelta));
-    };
-
-    const int l16 = lane & 15, lg = lane >> 4;
-    const int fo = (lg ^ duo_swz(l16)) << 4;     // this lane's chunk lg in any 16-row block
-    f32x4 acc[8][NB];
-#pragma unroll
-    for (int a = 0; a < 8; ++a)
-#pragma unroll
-        for (int b = 0; b < NB; ++b) acc[a][b] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-    SCD_STAMP_BEGIN();
-    // fragments of stage k are read in iteration k and used by the MFMAs of iteration k + 1 (two register sets, X / Y):
-    // the reads' latency hides behind the previous stage's MFMAs, and the next stage's DMA issues sit between them
-    h16x8 bx[NB], ax[8], by[NB], ay[8];
-    auto read_frags = [&](const char* As, h16x8 (&bf)[NB], h16x8 (&af)[8]) {
-        const char* Bs = As + BM * ROWB;
-#pragma unroll
-        for (int b = 0; b < NB; ++b) bf[b] = *(const h16x8*)(Bs + (64 * wn + 16 * b + l16) * ROWB + fo);
-#pragma unroll
-        for (int a = 0; a < 8; ++a) af[a] = *(const h16x8*)(As + (128 * wm + 16 * a + l16) * ROWB + fo);
-    };
-    auto mfmas = [&](const h16x8 (&bf)[NB], const h16x8 (&af)[8]) {
-        if constexpr (DUO_PRIO && !DUO_ILV) __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int a = 0; a < 8; ++a)
-#pragma unroll
-            for (int b = 0; b < NB; ++b)
-                acc[a][b] = mfma_16x16x32_h16(bf[b], af[a], acc[a][b]);
-        if constexpr (DUO_PRIO && !DUO_ILV) __builtin_amdgcn_s_setprio(0);
-    };
-    // one K-step k >= 1: stage k landed everywhere (this wave: vmcnt(6) leaves stage k + 1's 6 in flight; its reads
-    // of stage k - 1 drained: lgkmcnt(0), long done by now) -> barrier -> stage k + 2 into stage k - 1's slot ->
-    // read stage k into (bn, an) -> MFMAs of stage k - 1 from (bo, ao)
-    auto step = [&](int kt, int& cur, h16x8 (&bn)[NB], h16x8 (&an)[8], const h16x8 (&bo)[NB],
-                    const h16x8 (&ao)[8]) {
-        const StageArgs g = stage_args(kt + 2);
-        asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        const int nxs = cur == 0 ? 2 : cur - 1;
-        if constexpr (!DUO_ILV) {
-            issue(g, smem + nxs * STAGE);
-            read_frags(smem + cur * STAGE, bn, an);
-            mfmas(bo, ao);
-        } else {
-            // written in the interleaved order (the LDS-DMA builtin is a scheduling boundary, so the source order is
-            // the issue order): per group one DMA issue, two fragment reads, four MFMAs of the previous stage
-            if constexpr (DUO_PRIO) __builtin_amdgcn_s_setprio(1);
-            char* nb = smem + nxs * STAGE;
-            const char* As = smem + cur * STAGE;
-            const char* Bs = As + BM * ROWB;
-#pragma unroll
-            for (int q = 0; q < 8; ++q) {
-                if (q < 4) {
-                    const bool ok = g.live && ((a_mask[q] >> g.tap) & 1u);
-                    dma16(xrs, nb + (64 * wave + 16 * q) * ROWB, sel_off(ok, a_base[q] + g.adelta));
-                } else if (q < 6) {
-                    const int j = q - 4;
-                    dma16(wrs, nb + BM * ROWB + (32 * wave + 16 * j) * ROWB,
-                          sel_off(g.live && b_ok[j], b_base[j] + g.bdelta));
-                }
-                if (q < 2) {
-                    bn[2 * q] = *(const h16x8*)(Bs + (64 * wn + 16 * (2 * q) + l16) * ROWB + fo);
-                    bn[2 * q + 1] = *(const h16x8*)(Bs + (64 * wn + 16 * (2 * q + 1) + l16) * ROWB + fo);
-                } else if (q < 6) {
-                    const int a0 = 2 * (q - 2);
-                    an[a0] = *(const h16x8*)(As + (128 * wm + 16 * a0 + l16) * ROWB + fo);
-                    an[a0 + 1] = *(const h16x8*)(As + (128 * wm + 16 * (a0 + 1) + l16) * ROWB + fo);
-                }
-#pragma unroll
-                for (int b = 0; b < NB; ++b)
-                    acc[q][b] = mfma_16x16x32_h16(bo[b], ao[q], acc[q][b]);
-            }
-            if constexpr (DUO_PRIO) __builtin_amdgcn_s_setprio(0);
-        }
-        cur = cur == 2 ? 0 : cur + 1;
-    };
-    issue(stage_args(0), smem);
-    issue(stage_args(1), smem + STAGE);
-    {
-        asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        issue(stage_args(2), smem + 2 * STAGE);
-        read_frags(smem, by, ay);
-    }
-    int cur = 1;                                  // ring slot of stage kt
-    int kt = 1;
-    for (; kt + 1 < KT; kt += 2) {                // KT is even: pairs of steps 1..KT-2, then step KT-1
-        step(kt, cur, bx, ax, by, ay);
-        step(kt + 1, cur, by, ay, bx, ax);
-    }
-    step(kt, cur, bx, ax, by, ay);
-    mfmas(bx, ax);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    SCD_STAMP_END();
-
-    // ---- epilogue (the ping-pong kernel's, per wave 128 x 64): bias / relu, BN partial sums, the wave's tile staged in
-    // the ring, coalesced 16-B NHWC stores (+= when accumulating; the BN-backward sums from the stored gradient)
-    const int grp = wm, wc = wn;
-    char* ep = smem + wave * 128 * EROW;
-    float csum[NB][4], csq[NB][4];
-#pragma unroll
-    for (int b = 0; b < NB; ++b)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { csum[b][r] = 0.f; csq[b][r] = 0.f; }
-    constexpr int CPR = WCOLS * 2 / 16;                      // 8 chunks per staged row
-    struct PixPos { int n, qh, qw; };
-    auto pix_of = [&](int m) -> PixPos {
-        PixPos q;
-        q.n = m / QQ;
-        const int rem = m - q.n * QQ;
-        q.qh = rem / ph.Qw;
-        q.qw = rem - q.qh * ph.Qw;
-        return q;
-    };
-    auto pix_advance = [&](PixPos& q, int step) {
-        q.qw += step;
-        while (q.qw >= ph.Qw) {
-            q.qw -= ph.Qw;
-            if (++q.qh == ph.Qh) { q.qh = 0; ++q.n; }
-        }
-    };
-    auto out_off = [&](const PixPos& q, int col) -> long {
-        const int oh = p.os * q.qh + ph.rho_h, ow = p.os * q.qw + ph.rho_w;
-        if (p.shuf) {
-            const int c4 = p.Co >> 2, sp = col / c4;
-            return ((long)(q.n * 2 * p.Ho + 2 * oh + (sp >> 1)) * (2 * p.Wo) + 2 * ow + (sp & 1)) * c4 + (col - sp * c4);
-        }
-        return ((long)(q.n * p.Ho + oh) * p.Wo + ow) * p.Co + col;
-    };
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-        const int col0 = nt * BN + wc * WCOLS + b * 16 + lg * 4;
-        float bias[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) bias[r] = (p.bias && col0 + r < p.Co) ? p.bias[col0 + r] : 0.f;
-#pragma unroll
-        for (int a = 0; a < 8; ++a) {
-            const int m = mt * BM + 128 * grp + a * 16 + l16;
-            float v[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                v[r] = acc[a][b][r] + bias[r];
-                if (p.relu) v[r] = fmaxf(v[r], 0.f);
-            }
-            if (!p.bnbwd) {
-                const bool mok = m < M;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float t = mok ? v[r] : 0.f;
-                    csum[b][r] += t;
-                    csq[b][r] += t * t;
-                }
-            }
-            typedef __attribute__((ext_vector_type(4))) h16 bf16x4;
-            bf16x4 o = {(h16)v[0], (h16)v[1], (h16)v[2], (h16)v[3]};
-            *(bf16x4*)(ep + (a * 16 + l16) * EROW + (b * 16 + lg * 4) * 2) = o;
-        }
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // the staged tile is wave-private
-    constexpr int RPI = 64 / CPR;                            // 8 rows per pass
-    constexpr int NIT = 128 / RPI;
-    const int rsub = lane / CPR, chx = lane - (lane / CPR) * CPR;
-    float bs8[EPC], bq8[EPC];
-    if (p.bnbwd) {
-        const int colb = nt * BN + wc * WCOLS + chx * EPC;
-        const bool cok = colb < p.Co;
-        const int cl = cok ? colb : 0;
-        float mu[EPC], is[EPC], sc[EPC], sh[EPC];
-#pragma unroll
-        for (int e = 0; e < EPC; e += 4) {
-            const float4 f0 = *(const float4*)(p.bn_mean + cl + e), f1 = *(const float4*)(p.bn_invstd + cl + e);
-            const float4 f2 = *(const float4*)(p.bn_rsc + cl + e), f3 = *(const float4*)(p.bn_rsh + cl + e);
-            mu[e] = f0.x; mu[e + 1] = f0.y; mu[e + 2] = f0.z; mu[e + 3] = f0.w;
-            is[e] = f1.x; is[e + 1] = f1.y; is[e + 2] = f1.z; is[e + 3] = f1.w;
-            sc[e] = f2.x; sc[e + 1] = f2.y; sc[e + 2] = f2.z; sc[e + 3] = f2.w;
-            sh[e] = f3.x; sh[e + 1] = f3.y; sh[e + 2] = f3.z; sh[e + 3] = f3.w;
-        }
-#pragma unroll
-        for (int e = 0; e < EPC; ++e) { bs8[e] = 0.f; bq8[e] = 0.f; }
-        PixPos pq = pix_of(mt * BM + 128 * grp + rsub);
-#pragma unroll 4
-        for (int it = 0; it < NIT; ++it) {
-            const int row = it * RPI + rsub;
-            const int m = mt * BM + 128 * grp + row;
-            const bool ok = cok && m < M;
-            const long off = ok ? out_off(pq, cl) : 0;
-            pix_advance(pq, RPI);
-            uint4 v = *(const uint4*)(ep + row * EROW + chx * 16);
-            T* dst = (T*)(p.y) + off;
-            if (p.accumulate) {
-                float a8[EPC], o8[EPC];
-                Vec16<T>::load(&v, a8);
-                Vec16<T>::load(dst, o8);
-#pragma unroll
-                for (int e = 0; e < EPC; ++e) a8[e] += o8[e];
-                Vec16<T>::store(&v, a8);
-            }
-            float d8[EPC], y8[EPC];
-            Vec16<T>::load(&v, d8);
-            Vec16<T>::load((const T*)p.bny + off, y8);
-            if (ok) {
-#pragma unroll
-                for (int e = 0; e < EPC; ++e) {
-                    const float dz = y8[e] * sc[e] + sh[e] > 0.f ? d8[e] : 0.f;
-                    bs8[e] += dz;
-                    bq8[e] += dz * (y8[e] - mu[e]) * is[e];
-                }
-                *(uint4*)dst = v;
-            }
-        }
-    } else {
-        const int col = nt * BN + wc * WCOLS + chx * EPC;
-        PixPos pq = pix_of(mt * BM + 128 * grp + rsub);
-#pragma unroll 4
-        for (int it = 0; it < NIT; ++it) {
-            const int row = it * RPI + rsub;
-            const int m = mt * BM + 128 * grp + row;
-            const bool ok = m < M && col < p.Co;
-            T* dst = (T*)(p.y) + (ok ? out_off(pq, col) : 0);
-            pix_advance(pq, RPI);
-            uint4 v = *(const uint4*)(ep + row * EROW + chx * 16);
-            if (p.accumulate) {
-                float a[EPC], o[EPC];
-                Vec16<T>::load(&v, a);
-                Vec16<T>::load(dst, o);
-#pragma unroll
-                for (int e = 0; e < EPC; ++e) a[e] += o[e];
-                Vec16<T>::store(&v, a);
-            }
-            if (ok) *(uint4*)dst = v;
-        }
-    }
-    if (p.stats) {
-        float* red = (float*)(smem + (RING > EPI ? RING : EPI));    // [2 groups][BN][2]
-        if (p.bnbwd) {
-            float* part = (float*)ep;                        // [64 lanes][2 * EPC]
-#pragma unroll
-            for (int e = 0; e < EPC; ++e) { part[lane * 2 * EPC + e] = bs8[e]; part[lane * 2 * EPC + EPC + e] = bq8[e]; }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            if (lane < WCOLS) {
-                const int cx = lane / EPC, e = lane - (lane / EPC) * EPC;
-                float s = 0.f, q = 0.f;
-                for (int r = 0; r < RPI; ++r) {
-                    s += part[(r * CPR + cx) * 2 * EPC + e];
-                    q += part[(r * CPR + cx) * 2 * EPC + EPC + e];
-                }
-                red[(grp * BN + wc * WCOLS + lane) * 2 + 0] = s;
-                red[(grp * BN + wc * WCOLS + lane) * 2 + 1] = q;
-            }
-        } else {
-#pragma unroll
-            for (int b = 0; b < NB; ++b)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float s = row16_sum(csum[b][r]), q = row16_sum(csq[b][r]);
-                    if (l16 == 0) {
-                        const int c = wc * WCOLS + b * 16 + lg * 4 + r;
-                        red[(grp * BN + c) * 2 + 0] = s;
-                        red[(grp * BN + c) * 2 + 1] = q;
-                    }
-                }
-        }
-        __syncthreads();
-        if (tid < BN) {
-            const int col = nt * BN + tid;
-            if (col < p.Co) {
-                const double s = (double)red[tid * 2] + (double)red[(BN + tid) * 2];
-                const double q = (double)red[tid * 2 + 1] + (double)red[(BN + tid) * 2 + 1];
-                const int rep = bid % SCD_STAT_REPLICAS;
-                atomic_add_f64(p.stats + ((long)rep * 2 + 0) * p.Co + col, s);
-                atomic_add_f64(p.stats + ((long)rep * 2 + 1) * p.Co + col, q);
             }
         }
     }
@@ -2241,7 +1783,7 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_heads384_kernel(GemmParams p
         auto mfma_q = [&](int q) {
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_sched_barrier(0);
-            if constexpr (PP_PRIO == 1) __builtin_amdgcn_s_setprio(1);
+            __builtin_amdgcn_s_setprio(1);
     #pragma unroll
             for (int s = 0; s < 2; ++s)
     #pragma unroll
@@ -2249,7 +1791,7 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_heads384_kernel(GemmParams p
     #pragma unroll
                     for (int b = 0; b < NB; ++b)
                         acc[2 * q + a][b] = mfma_16x16x32_h16(bfr[b][s], af[a][s], acc[2 * q + a][b]);
-            if constexpr (PP_PRIO == 1) __builtin_amdgcn_s_setprio(0);
+            __builtin_amdgcn_s_setprio(0);
             __builtin_amdgcn_sched_barrier(0);
         };
         auto bar = [&]() {
@@ -2263,7 +1805,6 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_heads384_kernel(GemmParams p
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             bar();
             if (grp == 1) bar();                 // stagger: group 1 runs one barrier behind
-            if constexpr (PP_PRIO == 2) { if (grp == 1) __builtin_amdgcn_s_setprio(1); }
             for (int t = 0; t < KT; ++t) {
                 char* cur = smem + (t & 1) * STAGE;
                 char* nxt = smem + ((t & 1) ^ 1) * STAGE;
@@ -2294,7 +1835,6 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_heads384_kernel(GemmParams p
                 bar();
             }
             if (grp == 0) bar();
-            if constexpr (PP_PRIO == 2) __builtin_amdgcn_s_setprio(0);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
@@ -2417,6 +1957,8 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_heads384_kernel(GemmParams p
         __syncthreads();                 // staging consumed before the next tile's prologue DMA
     }
 }
+
+constexpr int WGRAD_OCC = 2;  // register-staged weight-gradient kernel: workgroups per CU the registers are budgeted for
 
 // -------------------------------------------------------------------------------------
 // weight gradient: ws[z][co][t*Ci+ci] = sum_pix g[pix][co] * x[gather(pix,t)][ci]
@@ -2750,10 +2292,8 @@ __device__ __forceinline__ int wr_f(int r) { return (r & 3) | ((r >> 1) & 4); }
 // fetched in phases 1/2.  Counted waits as conv_gemm_pp_kernel (NB2 = 2).  Requires Wo % 64 == 0 and
 // (Ho*Wo) % 64 == 0: a stage is part of one output row, addressed by a scalar cursor (see FASTX 1).
 // NQ 2 (48-KB stages, half the MFMAs per stage of NQ 4): three stage buffers, two stages of DMA in flight -- a stage
-// is ~1000 MFMA cycles, shorter than the operand fetch latency under load (SCD_PP2_NBUF=2: two buffers).
-#ifndef SCD_PP2_NBUF
-#define SCD_PP2_NBUF 3
-#endif
+// is ~1000 MFMA cycles, shorter than the operand fetch latency under load.
+constexpr int SCD_PP2_NBUF = 3;
 template <int NQ>
 __global__ __launch_bounds__(512, 1) void conv_wgrad_pp2_kernel(WgradParams p) {
     constexpr int KP = 64, EPC = 8;
@@ -2891,7 +2431,7 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_pp2_kernel(WgradParams p) {
     auto mfma_q = [&](int q, const h16x8 (&gf)[2][2]) {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (PP_PRIO == 1) __builtin_amdgcn_s_setprio(1);
+        __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int s = 0; s < 2; ++s)
 #pragma unroll
@@ -2899,7 +2439,7 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_pp2_kernel(WgradParams p) {
 #pragma unroll
                 for (int b = 0; b < 4; ++b)
                     acc[2 * q + a][b] = mfma_16x16x32_h16(xf[b][s], gf[a][s], acc[2 * q + a][b]);
-        if constexpr (PP_PRIO == 1) __builtin_amdgcn_s_setprio(0);
+        __builtin_amdgcn_s_setprio(0);
         __builtin_amdgcn_sched_barrier(0);
     };
     auto bar = [&]() {
@@ -2928,7 +2468,6 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_pp2_kernel(WgradParams p) {
         }
         bar();
         if (grp == 1) bar();
-        if constexpr (PP_PRIO == 2) { if (grp == 1) __builtin_amdgcn_s_setprio(1); }
         // schedule (stage t fetches stage t+1 into the other buffer): phase 1: X half 0, phase 2: X half 1,
         // phases 3(-4): the G quarters.  NQ 4: C2 vmcnt(4), L4 vmcnt(4), C4 vmcnt(2);
         // NQ 3: C1 vmcnt(3), C2 vmcnt(4), L3 vmcnt(3), C3 vmcnt(2);
@@ -2993,7 +2532,6 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_pp2_kernel(WgradParams p) {
             }
         }
         if (grp == 0) bar();
-        if constexpr (PP_PRIO == 2) __builtin_amdgcn_s_setprio(0);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     // fp32 slab: lane holds columns kk..kk+3 of channel row cg for every (m, b) block
@@ -3404,7 +2942,7 @@ struct S1x1Plan {
     static constexpr int XU = 16 * UA * K * 2;                     // bytes of one pixel wave's unit
     static constexpr int XALL = 2 * (WV / SPL) * XU;               // two buffers per pixel wave
     static constexpr int OCC0 = 163840 / (WBYTES + PBYTES), OCC1 = 163840 / (WBYTES + PBYTES + XALL);
-    static constexpr bool STG = S1X1_STG && SPL > 1 && OCC1 >= 1 && (OCC1 >= 2 || OCC0 < 2);
+    static constexpr bool STG = SPL > 1 && OCC1 >= 1 && (OCC1 >= 2 || OCC0 < 2);
     static constexpr int XBYTES = STG ? XALL : 0;
 };
 template <int K, int N, int MODE, int SPL, int UA, int WV>
@@ -3462,14 +3000,14 @@ __global__ __launch_bounds__(64 * WV, 8 / WV) void conv1x1_stream_kernel(GemmPar
     for (int j = 0; j < NS; ++j) { ssum[j] = 0.f; ssq[j] = 0.f; }
     // lane's store column of channel-block pair (b, b + 1): even lg block b, odd lg block b + 1 (permlane16_swap)
     const int cst = c0w + 4 * lg + 12 * (lg & 1);
-    // S1X1_FULLROW: a lane's place in the whole-128-B-row layout of a 64-channel piece (pixel l16 & 7 of the first or
+    // whole-row stores: a lane's place in the whole-128-B-row layout of a 64-channel piece (pixel l16 & 7 of the first or
     // second 8 of a 16-pixel block, channels fr_cw .. + 7 of the piece; see the stores in unit())
     const bool fr_hi = l16 >= 8;
     const int fr_cw = 32 * (l16 >> 3) + (cst & 31);
     // the epilogue operands in that layout too where a wave holds one 64-channel piece (wider waves: their conversion
     // temporaries spill)
     // (not for the BN-backward-sum instances at K = 256, which then spill)
-    constexpr bool ST_FR = S1X1_FULLROW && !(MODE == 2 && K >= 256);
+    constexpr bool ST_FR = !(MODE == 2 && K >= 256);
     constexpr bool EPI_FR = ST_FR && NB == 4;
     auto ror8 = [](const uint4& v) {
         uint4 r;
@@ -3742,22 +3280,50 @@ __global__ __launch_bounds__(64 * WV, 8 / WV) void conv1x1_stream_kernel(GemmPar
     }
 }
 
+
 SCD_KERNEL_NS_END
 }  // namespace
 
-// conv1x1_stream_kernel: -1 when the shape is not one it takes, else the launch status.  SCD_GEMM_STREAM1X1 (read
-// per call: tests compare the kernels bit for bit): 0 keeps these shapes on the tiled kernels, 2 (tests) makes every
-// GEMM the stream kernel does not take fail with SCD_ERR_ARG
-static int stream1x1_mode() {
-    const char* e = getenv("SCD_GEMM_STREAM1X1");
-    return e ? atoi(e) : 1;
+static int num_cus() {
+    static int n = 0;
+    if (n == 0) {
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess ||
+            hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
+            n = 256;
+    }
+    return n;
 }
-// SCD_S1X1_OCC (read per call): at most this many stream workgroups per CU (0 / unset: as many as fit)
-static int s1x1_occ_cap() {
-    const char* e = getenv("SCD_S1X1_OCC");
-    return e ? atoi(e) : 0;
+
+// The tile table of a launch: ntn column tiles per BM pixels, the phases' tiles one after another.  Returns the tiles.
+static int fill_tiles(GemmParams& p, int nphase, const scd_gemm_phase* phases, int BM, int ntn) {
+    p.ntn = ntn;
+    int tiles = 0;
+    for (int i = 0; i < SCD_MAX_PHASES; ++i) {
+        p.tile_start[i] = tiles;
+        if (i < nphase) {
+            p.ph[i] = phases[i];
+            tiles += cdiv((long)p.N * phases[i].Qh * phases[i].Qw, BM) * ntn;
+        }
+    }
+    p.tile_start[SCD_MAX_PHASES] = tiles;
+    return tiles;
 }
-static int num_cus();
+
+// 32-bit buffer offsets: the byte ranges of the operand, the weights and (with_y) a tensor of the output's shape (the
+// pre-BN activation or the residual; else 0).  False when one does not fit: the caller returns SCD_ERR_ARG
+static bool fill_ranges(int dtype, GemmParams& p, bool with_y) {
+    const long esz = dtype == SCD_DT_BF16 ? 2 : 4, lim = (1L << 31) - 64;
+    const long xb = (long)p.N * p.Hi * p.Wi * p.Ci * esz, wb = (long)p.Co * p.wrow * esz;
+    const long yb = with_y ? (long)p.N * p.Ho * p.Wo * p.Co * esz : 0;
+    if (xb >= lim || wb >= lim || yb >= lim) return false;
+    p.xbytes = (int)xb; p.wbytes = (int)wb; p.ybytes = (int)yb;
+    return true;
+}
+
+// One launcher per kernel family, asked in order by conv_gemm_launch: -1 when the call (validated; Mtot = the phases'
+// pixels) is not the family's shape, else the launch status or SCD_ERR_ARG.  Each fills every GemmParams field its
+// kernel reads beyond fill_params' and conv_gemm_launch's nphase, and leaves p as it was when it declines.
 static int launch_stream1x1(int dtype, GemmParams& p, int nphase, const scd_gemm_phase* phases, long Mtot,
                             hipStream_t st) {
     if (dtype != SCD_DT_BF16 || stream1x1_mode() == 0) return -1;
@@ -3771,8 +3337,6 @@ static int launch_stream1x1(int dtype, GemmParams& p, int nphase, const scd_gemm
         return -1;
     const int K = p.Ci, N = p.Co;
     if (Mtot % 128 || Mtot < 65536 || Mtot * (long)(K > N ? K : N) >= (1L << 30)) return -1;
-    p.xbytes = (int)(Mtot * K * 2);                          // the operand's buffer range (LDS-DMA path)
-    if (res3) p.ybytes = (int)(Mtot * N * 2);                // the residual's
     const bool sums = p.stats != nullptr;                    // forward statistics or BN-backward sums
     if (p.accumulate && sums) return -1;
     const long nchunks = Mtot / 128;
@@ -3784,21 +3348,21 @@ static int launch_stream1x1(int dtype, GemmParams& p, int nphase, const scd_gemm
     const int Nd = attempt == 0 ? N : 256;
     if (attempt == 1 && (N <= 256 || N % 256)) break;
     const int nsl = N / Nd;
-    // about one round of resident workgroups: as many per CU as the instance's registers and LDS allow (capped by
-    // SCD_S1X1_OCC when set), so every workgroup of the grid runs in the first round
+    // about one round of resident workgroups: as many per CU as the instance's registers and LDS allow, so every
+    // workgroup of the grid runs in the first round.  True: the launch follows, and p has its buffer ranges
     auto plan = [&](const void* kern, int threads, int& per_cache, long& cpw, int& grid) -> bool {
         if (per_cache < 0) {
             int per = 1;
             if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kern, threads, 0) != hipSuccess || per < 1) per = 1;
             per_cache = per;
         }
-        const int cap = s1x1_occ_cap();
-        const long per = cap > 0 ? std::min(cap, per_cache) : per_cache;
-        const long want = std::max(1L, per * cus / nsl);
+        const long want = std::max(1L, per_cache * cus / nsl);
         cpw = 2;                                             // (even: the waves take units in pairs)
         while (nchunks / cpw > want && nchunks % (2 * cpw) == 0) cpw *= 2;
         if (nchunks % cpw) return false;
         grid = (int)(nchunks / cpw);
+        p.xbytes = (int)(Mtot * K * 2);                      // the operand's buffer range (LDS-DMA path)
+        p.ybytes = res3 ? (int)(Mtot * N * 2) : 0;           // the residual's
         return true;
     };
     long cpw = 0;
@@ -3807,7 +3371,7 @@ static int launch_stream1x1(int dtype, GemmParams& p, int nphase, const scd_gemm
     // with the BN-backward sums, whose registers it would spill)
 #define SCD_S1X1(KK, NN, MM, SS)                                                                                     \
     if (K == KK && Nd == NN && mode == MM) {                                                                         \
-        constexpr int UA_ = (S1X1_UA2 && KK == 64 && NN / SS <= 64 && MM != 2) ? 2 : 1;                              \
+        constexpr int UA_ = (KK == 64 && NN / SS <= 64 && MM != 2) ? 2 : 1;                                          \
         static int per_ = -1;                                                                                        \
         if (!plan((const void*)conv1x1_stream_kernel<KK, NN, MM, SS, UA_, 4>, 256, per_, cpw, grid)) return -1;      \
         hipLaunchKernelGGL((conv1x1_stream_kernel<KK, NN, MM, SS, UA_, 4>), dim3(grid, nsl), dim3(256), 0, st, p, (int)cpw); \
@@ -3853,91 +3417,53 @@ static int launch_stream1x1(int dtype, GemmParams& p, int nphase, const scd_gemm
     return -1;
 }
 
-// Kernel choice: the LDS-DMA ring kernel (256x128, bf16) for large outputs, the register-staged
-// 128x128 kernel otherwise, 256x64 for narrow outputs (Co <= 64).  SCD_GEMM_RING=0/1 forces it off/on.
-// Intra-workgroup split K of the register-staged 128x128 kernel (SCD_GEMM_KSPLIT: 0 off, 1 auto = grids of at
-// most 1.5 tiles per CU with >= 16 K stages, 2 always where it applies)
-static int ksplit_mode() {
-    static int mode = -1;
-    if (mode < 0) {
-        const char* e = getenv("SCD_GEMM_KSPLIT");
-        mode = e ? atoi(e) : 1;
-    }
-    return mode;
+// the three 128-wide CenterNet heads (bf16): one 192 x 384 tile per 192 pixels, tails fused
+static int launch_heads384(int dtype, GemmParams& p, int nphase, const scd_gemm_phase* phases, long /*Mtot*/,
+                           hipStream_t st) {
+    if (!(p.head_on && dtype == SCD_DT_BF16 && nphase == 1 && p.Co == 384 && p.head_out[0] && p.head_out[1] &&
+          p.head_out[2] && !p.head_out[3] && p.is == 1 && p.os == 1 && p.Ho == phases[0].Qh && p.Wo == phases[0].Qw &&
+          p.bias && p.relu && !p.accumulate && !p.stats))
+        return -1;
+    if (!fill_ranges(dtype, p, false)) return SCD_ERR_ARG;
+    const int tiles = fill_tiles(p, nphase, phases, 192, 1);
+    hipLaunchKernelGGL(conv_gemm_heads384_kernel, dim3(tiles), dim3(512), 0, st, p);
+    SCD_RETURN_LAUNCH();
 }
 
-static int ring_mode() {
-    static int mode = -2;
-    if (mode == -2) {
-        const char* e = getenv("SCD_GEMM_RING");
-        mode = e ? atoi(e) : -1;
-    }
-    return mode;
-}
-
-static int narrow_ring_mode() {
-    // SCD_GEMM_NARROW_RING=0: narrow 1x1 shapes on the register-staged 256 x 64 kernel (read per call: A/B).  On the
-    // ring kernel: Res50 1024^2 fp16 +0.4 % (the 256 x 64 kernel's 88 launches of 268 us per 11 steps become ring
-    // launches), Res10 neutral (profiles/r4_ab.txt)
-    const char* e = getenv("SCD_GEMM_NARROW_RING");
-    return e ? atoi(e) : 1;
-}
-static int pp_mode() {
-    static int mode = -2;
-    if (mode == -2) {
-        const char* e = getenv("SCD_GEMM_PP");
-        mode = e ? atoi(e) : 1;
-    }
-    return mode;
-}
-
-static int duo_mode() {
-    // SCD_GEMM_DUO (read per call: tests compare the kernels): 0 = off, 1 = the ping-pong shapes (Co % 256 / 192 == 0)
-    // on the two-workgroups-per-CU kernel, 2 = also the 256 x 128 ring shapes (Co % 128 == 0), 3 = only the ping-pong
-    // shapes with the BN-backward-sum epilogue and >= 8 rounds of duo tiles (where the epilogue is what the two
-    // workgroups per CU overlap: the heatmap-head input gradient; tools/duo_probe.py), 4 = only the ring shapes
-    // (Co % 128 == 0, not a ping-pong width: the layer2 convs at 128 channels)
-    const char* e = getenv("SCD_GEMM_DUO");
-    return e ? atoi(e) : 0;
-}
-
-static int duo_delay_pct() {
-    const char* e = getenv("SCD_DUO_DELAY");
-    return e ? atoi(e) : 100;
-}
-
-static int heads384_mode() {
-    static int mode = -2;
-    if (mode == -2) {
-        const char* e = getenv("SCD_GEMM_HEADS384");
-        mode = e ? atoi(e) : 1;
-    }
-    return mode;
-}
-
-static int num_cus() {
-    static int n = 0;
-    if (n == 0) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-            n = 256;
-    }
-    return n;
-}
-
-static int pp_bn(int dtype, int Co) {
+// bf16, Co a multiple of 256 or 192, and a grid that fills the chip
+static int pp_tile_bn(int dtype, int Co, long Mtot) {
     if (dtype != SCD_DT_BF16 || !pp_mode()) return 0;
-    if (Co % 256 == 0) return 256;
-    if (Co % 192 == 0) return 192;
-    return 0;
+    const int bn = Co % 256 == 0 ? 256 : (Co % 192 == 0 ? 192 : 0);
+    return bn && (long)cdiv(Mtot, 256) * (Co / bn) >= 256 ? bn : 0;
 }
 
-static int halo64_mode() {
-    // SCD_GEMM_HALO64=0: the register-staged kernel.  Read per launch (not cached): tests switch it to compare the
-    // two bit for bit
-    const char* e = getenv("SCD_GEMM_HALO64");
-    return e ? atoi(e) : 1;
+// (fused head tails are run as a separate pass)
+static int launch_pp(int dtype, GemmParams& p, int nphase, const scd_gemm_phase* phases, long Mtot,
+                     hipStream_t st) {
+    const int bn = pp_tile_bn(dtype, p.Co, Mtot);
+    if (!bn) return -1;
+    const int tiles = fill_tiles(p, nphase, phases, 256, p.Co / bn);
+    if (!fill_ranges(dtype, p, p.bnbwd || p.res)) return SCD_ERR_ARG;
+    if (p.head_on) {
+        // heads split between two column tiles accumulate two partial sums: zero them first
+        for (int h = 0; h < 4 && p.head_out[h]; ++h)
+            if ((h * 128) / bn != (h * 128 + 127) / bn) {
+                hipError_t e = hipMemsetAsync(p.head_out[h], 0, sizeof(float) * p.head_od[h] * (size_t)p.N * p.Ho * p.Wo, st);
+                if (e != hipSuccess) return (int)e;
+            }
+        if (bn == 256) hipLaunchKernelGGL((conv_gemm_pp_kernel<256, true>), dim3(tiles), dim3(512), 0, st, p);
+        else hipLaunchKernelGGL((conv_gemm_pp_kernel<192, true>), dim3(tiles), dim3(512), 0, st, p);
+    } else if (p.bnbwd) {
+        if (bn == 256) hipLaunchKernelGGL((conv_gemm_pp_kernel<256, false, true>), dim3(tiles), dim3(512), 0, st, p);
+        else hipLaunchKernelGGL((conv_gemm_pp_kernel<192, false, true>), dim3(tiles), dim3(512), 0, st, p);
+    } else if (p.res) {
+        if (bn == 256) hipLaunchKernelGGL((conv_gemm_pp_kernel<256, false, false, true>), dim3(tiles), dim3(512), 0, st, p);
+        else hipLaunchKernelGGL((conv_gemm_pp_kernel<192, false, false, true>), dim3(tiles), dim3(512), 0, st, p);
+    } else {
+        if (bn == 256) hipLaunchKernelGGL((conv_gemm_pp_kernel<256, false>), dim3(tiles), dim3(512), 0, st, p);
+        else hipLaunchKernelGGL((conv_gemm_pp_kernel<192, false>), dim3(tiles), dim3(512), 0, st, p);
+    }
+    SCD_RETURN_LAUNCH();
 }
 
 // conv_gemm_l1p_kernel's shapes: one phase of the 9 taps of a 3x3 / stride 1 / pad 1 convolution in the forward
@@ -3960,145 +3486,23 @@ static int halo64_taps(const GemmParams& p, int nphase, const scd_gemm_phase* ph
     return fwd ? 0 : (bwd ? 1 : -1);
 }
 
-static int conv_gemm_launch(int dtype, GemmParams& p, int nphase, const scd_gemm_phase* phases, void* stream) {
-    if (nphase < 1 || nphase > SCD_MAX_PHASES) return SCD_ERR_ARG;
-    const int BK = dtype == SCD_DT_BF16 ? 64 : 32;
-    const int EPC = dtype == SCD_DT_BF16 ? 8 : 4;
-    if (p.Ci % BK != 0 || p.Co <= 0 || p.Co % EPC != 0 || p.N <= 0) return SCD_ERR_ARG;
-    p.nphase = nphase;
-    const int esz = dtype == SCD_DT_BF16 ? 2 : 4;
-    const long xb = (long)p.N * p.Hi * p.Wi * p.Ci * esz;
-    const bool narrow = p.Co <= 64;
-    if (p.head_on && (narrow || p.Co != 128 * ((p.Co + 127) / 128))) return SCD_ERR_ARG;
-    long Mtot = 0;
-    for (int i = 0; i < nphase; ++i) {
-        if (phases[i].ntaps < 0 || phases[i].ntaps > SCD_MAX_TAPS) return SCD_ERR_ARG;
-        for (int t = 0; t < phases[i].ntaps; ++t)
-            if (phases[i].wt[t] < 0 || (long)(phases[i].wt[t] + 1) * p.Ci > p.wrow) return SCD_ERR_ARG;
-        Mtot += (long)p.N * phases[i].Qh * phases[i].Qw;
-    }
-    {
-        const int rc = launch_stream1x1(dtype, p, nphase, phases, Mtot, (hipStream_t)stream);
-        if (rc >= 0) return rc;
-        if (stream1x1_mode() == 2) return SCD_ERR_ARG;
-    }
-    if (p.head_on && dtype == SCD_DT_BF16 && heads384_mode() && nphase == 1 && p.Co == 384 && p.head_out[0] &&
-        p.head_out[1] && p.head_out[2] && !p.head_out[3] && p.is == 1 && p.os == 1 && p.Ho == phases[0].Qh &&
-        p.Wo == phases[0].Qw && p.bias && p.relu && !p.accumulate && !p.stats) {
-        // the three 128-wide CenterNet heads: one 192 x 384 tile per 192 pixels, tails fused
-        const long wb = (long)p.Co * p.wrow * esz;
-        if (xb >= (1L << 31) - 64 || wb >= (1L << 31) - 64) return SCD_ERR_ARG;
-        p.xbytes = (int)xb;
-        p.wbytes = (int)wb;
-        p.ntn = 1;
-        p.ph[0] = phases[0];
-        for (int i = 0; i <= SCD_MAX_PHASES; ++i) p.tile_start[i] = 0;
-        const int tiles = cdiv(Mtot, 192);
-        hipLaunchKernelGGL(conv_gemm_heads384_kernel, dim3(tiles), dim3(512), 0, (hipStream_t)stream, p);
-        SCD_RETURN_LAUNCH();
-    }
-    {
-        // two 256 x 128 workgroups per CU (conv_gemm_duo_kernel) where the grid gives each CU >= 2 tiles
-        const int dm = duo_mode();
-        const bool shape = dtype == SCD_DT_BF16 && !p.head_on && !p.res && p.Co % 128 == 0 &&
-                           (dm == 4 ? !pp_bn(dtype, p.Co) : (pp_bn(dtype, p.Co) || dm >= 2));
-        const long dtiles = (long)cdiv(Mtot, 256) * (p.Co / 128);
-        const bool take = dm == 3 ? (p.bnbwd && dtiles >= 16L * num_cus()) : dtiles >= 2L * num_cus();
-        if (dm && shape && take) {
-            p.ntn = p.Co / 128;
-            int tiles = 0;
-            int ktmax = 0;
-            for (int i = 0; i < SCD_MAX_PHASES; ++i) {
-                p.tile_start[i] = tiles;
-                if (i < nphase) {
-                    p.ph[i] = phases[i];
-                    tiles += cdiv((long)p.N * phases[i].Qh * phases[i].Qw, 256) * p.ntn;
-                    ktmax = std::max(ktmax, phases[i].ntaps * (p.Ci / 64) * 2);
-                }
-            }
-            p.tile_start[SCD_MAX_PHASES] = tiles;
-            const long wb = (long)p.Co * p.wrow * esz;
-            if (xb >= (1L << 31) - 64 || wb >= (1L << 31) - 64) return SCD_ERR_ARG;
-            p.xbytes = (int)xb;
-            p.wbytes = (int)wb;
-            // half a tile: ~KT x 32 MFMAs x 16 cycles x 2 workgroups sharing the matrix pipe / 2, at ~75 % of it, in
-            // s_sleep(127) quanta of 8,128 cycles
-            p.duo_ncu = num_cus();
-            p.duo_delay = (int)((long)ktmax * 680 * duo_delay_pct() / 100 / 8128);
-            hipLaunchKernelGGL(conv_gemm_duo_kernel, dim3(tiles), dim3(256), 0, (hipStream_t)stream, p);
-            SCD_RETURN_LAUNCH();
-        }
-    }
-    {
-        // ping-pong 256 x BN kernel when the grid fills the chip (fused head tails are run as a separate pass)
-        const int bn = pp_bn(dtype, p.Co);
-        if (bn && (long)cdiv(Mtot, 256) * (p.Co / bn) >= 256) {
-            p.ntn = p.Co / bn;
-            int tiles = 0;
-            for (int i = 0; i < SCD_MAX_PHASES; ++i) {
-                p.tile_start[i] = tiles;
-                if (i < nphase) {
-                    p.ph[i] = phases[i];
-                    tiles += cdiv((long)p.N * phases[i].Qh * phases[i].Qw, 256) * p.ntn;
-                }
-            }
-            p.tile_start[SCD_MAX_PHASES] = tiles;
-            const long wb = (long)p.Co * p.wrow * esz;
-            if (xb >= (1L << 31) - 64 || wb >= (1L << 31) - 64) return SCD_ERR_ARG;
-            p.xbytes = (int)xb;
-            p.wbytes = (int)wb;
-            const long yb = (p.bnbwd || p.res) ? (long)p.N * p.Ho * p.Wo * p.Co * esz : 0;
-            if (yb >= (1L << 31) - 64) return SCD_ERR_ARG;
-            p.ybytes = (int)yb;
-            hipStream_t st = (hipStream_t)stream;
-            if (p.head_on) {
-                // heads split between two column tiles accumulate two partial sums: zero them first
-                for (int h = 0; h < 4 && p.head_out[h]; ++h)
-                    if ((h * 128) / bn != (h * 128 + 127) / bn) {
-                        hipError_t e = hipMemsetAsync(p.head_out[h], 0, sizeof(float) * p.head_od[h] * (size_t)p.N * p.Ho * p.Wo, st);
-                        if (e != hipSuccess) return (int)e;
-                    }
-                if (bn == 256) hipLaunchKernelGGL((conv_gemm_pp_kernel<256, true>), dim3(tiles), dim3(512), 0, st, p);
-                else hipLaunchKernelGGL((conv_gemm_pp_kernel<192, true>), dim3(tiles), dim3(512), 0, st, p);
-            } else if (p.bnbwd) {
-                if (bn == 256) hipLaunchKernelGGL((conv_gemm_pp_kernel<256, false, true>), dim3(tiles), dim3(512), 0, st, p);
-                else hipLaunchKernelGGL((conv_gemm_pp_kernel<192, false, true>), dim3(tiles), dim3(512), 0, st, p);
-            } else if (p.res) {
-                if (bn == 256) hipLaunchKernelGGL((conv_gemm_pp_kernel<256, false, false, true>), dim3(tiles), dim3(512), 0, st, p);
-                else hipLaunchKernelGGL((conv_gemm_pp_kernel<192, false, false, true>), dim3(tiles), dim3(512), 0, st, p);
-            } else {
-                if (bn == 256) hipLaunchKernelGGL((conv_gemm_pp_kernel<256, false>), dim3(tiles), dim3(512), 0, st, p);
-                else hipLaunchKernelGGL((conv_gemm_pp_kernel<192, false>), dim3(tiles), dim3(512), 0, st, p);
-            }
-            SCD_RETURN_LAUNCH();
-        }
-    }
-    if (p.bnbwd && dtype != SCD_DT_BF16) return SCD_ERR_ARG;   // BN-backward sums: 16-bit epilogues (caller falls back)
-    {
-        // 3x3 / s1 / p1, 64 -> 64 channels on whole rows of 64, 128 or 256 pixels: the persistent row-ring kernel
-        const int flip = halo64_taps(p, nphase, phases);
-        // scd_conv_gemm_res: its forward variant with the bias / residual / ReLU epilogue
-        const bool l1res = p.resmode && (p.bias || p.relu || p.res);
-        if (dtype == SCD_DT_BF16 && flip >= 0 && halo64_mode() &&
-            (l1res ? (flip == 0 && !p.stats && !p.accumulate && !p.bnbwd) : (!p.bias && !p.relu && !p.res))) {
-            if (p.Wo == 256 && p.bnbwd) return SCD_ERR_ARG;    // scd_conv_gemm_bnbwd: this kernel + separate reduce
-            p.ntn = 1;
-            p.ph[0] = phases[0];
-            for (int i = 0; i <= SCD_MAX_PHASES; ++i) p.tile_start[i] = 0;
-            const long wb = (long)p.Co * p.wrow * esz;
-            if (xb >= (1L << 31) - 64 || wb >= (1L << 31) - 64) return SCD_ERR_ARG;
-            p.xbytes = (int)xb;
-            p.wbytes = (int)wb;
-            const long yb = l1res ? (long)p.N * p.Ho * p.Wo * p.Co * esz : 0;
-            if (yb >= (1L << 31) - 64) return SCD_ERR_ARG;
-            p.ybytes = (int)yb;
-            const int tiles = (int)(Mtot / 256);
-            hipStream_t st = (hipStream_t)stream;
-            // `run` tiles per workgroup down one image (about one workgroup per CU)
-            const int tpi = p.Wo >= 256 ? p.Ho : p.Ho / (256 / p.Wo);
-            int run = 1;
-            while (run < 16 && tpi % (2 * run) == 0 && tiles / (2 * run) >= num_cus()) run *= 2;
-            const int grid = tiles / run;
+// 3x3 / s1 / p1, 64 -> 64 channels on whole rows of 64, 128 or 256 pixels: the persistent row-ring kernel
+static int launch_l1p(int dtype, GemmParams& p, int nphase, const scd_gemm_phase* phases, long /*Mtot*/,
+                      hipStream_t st) {
+    const int flip = halo64_taps(p, nphase, phases);
+    // scd_conv_gemm_res: its forward variant with the bias / residual / ReLU epilogue
+    const bool l1res = p.resmode && (p.bias || p.relu || p.res);
+    if (dtype != SCD_DT_BF16 || flip < 0 || !halo64_mode() ||
+        !(l1res ? (flip == 0 && !p.stats && !p.accumulate && !p.bnbwd) : (!p.bias && !p.relu && !p.res)))
+        return -1;
+    if (p.Wo == 256 && p.bnbwd) return SCD_ERR_ARG;    // scd_conv_gemm_bnbwd: this kernel + separate reduce
+    const int tiles = fill_tiles(p, nphase, phases, 256, 1);
+    if (!fill_ranges(dtype, p, l1res)) return SCD_ERR_ARG;
+    // `run` tiles per workgroup down one image (about one workgroup per CU)
+    const int tpi = p.Wo >= 256 ? p.Ho : p.Ho / (256 / p.Wo);
+    int run = 1;
+    while (run < 16 && tpi % (2 * run) == 0 && tiles / (2 * run) >= num_cus()) run *= 2;
+    const int grid = tiles / run;
 #define SCD_L1P_LAUNCH(WO)                                                                                              \
     do {                                                                                                                 \
         if (l1res) {                                                                                                     \
@@ -4111,62 +3515,87 @@ static int conv_gemm_launch(int dtype, GemmParams& p, int nphase, const scd_gemm
             else hipLaunchKernelGGL((conv_gemm_l1p_kernel<WO, false, false>), dim3(grid), dim3(512), 0, st, p, run);     \
         }                                                                                                                \
     } while (0)
-            if (p.Wo == 256) SCD_L1P_LAUNCH(256);
-            else if (p.Wo == 128) SCD_L1P_LAUNCH(128);
-            else SCD_L1P_LAUNCH(64);
+    if (p.Wo == 256) SCD_L1P_LAUNCH(256);
+    else if (p.Wo == 128) SCD_L1P_LAUNCH(128);
+    else SCD_L1P_LAUNCH(64);
 #undef SCD_L1P_LAUNCH
-            SCD_RETURN_LAUNCH();
-        }
-    }
-    bool ring = false;
-    if (dtype == SCD_DT_BF16 && !narrow) {
+    SCD_RETURN_LAUNCH();
+}
+
+// The ring kernel (256 x 128, bf16) for large outputs: at least one tile per CU (SCD_GEMM_RING=0/1 forces it off / on).
+static int launch_ring(int dtype, GemmParams& p, int nphase, const scd_gemm_phase* phases, long Mtot,
+                       hipStream_t st) {
+    if (dtype != SCD_DT_BF16) return -1;
+    bool ring;
+    if (p.Co > 64) {
         const int rm = ring_mode();
-        ring = rm >= 0 ? rm != 0 : cdiv(Mtot, 256) * cdiv(p.Co, 128) >= 256;   // >= one tile per CU
-    } else if (dtype == SCD_DT_BF16 && narrow_ring_mode() && nphase == 1 && phases[0].ntaps == 1 && p.Ci >= 128 &&
-               cdiv(Mtot, 256) >= 256) {
+        ring = rm >= 0 ? rm != 0 : cdiv(Mtot, 256) * cdiv(p.Co, 128) >= 256;
+    } else {
         // 1x1 convs into <= 64 channels over many pixels (the Bottleneck conv1 forward and conv3 input gradient at
-        // Res50 1024^2, residuals.py:122-165): HBM-bound skinny GEMMs on the LDS-DMA ring kernel, half its 128-column
-        // tile empty, instead of the register-staged 256 x 64 kernel
-        ring = true;
+        // Res50 1024^2, residuals.py:122-165): HBM-bound skinny GEMMs on this kernel, half its 128-column tile empty,
+        // instead of the register-staged 256 x 64 kernel.  Res50 1024^2 fp16 +0.4 % (the 256 x 64 kernel's 88
+        // launches of 268 us per 11 steps become ring launches), Res10 neutral (profiles/r4_ab.txt)
+        ring = nphase == 1 && phases[0].ntaps == 1 && p.Ci >= 128 && cdiv(Mtot, 256) >= 256;
     }
-    const int BM = ring ? 256 : (narrow ? 256 : 128), BN = (narrow && !ring) ? 64 : 128;
-    p.ntn = cdiv(p.Co, BN);
-    int tiles = 0;
-    for (int i = 0; i < SCD_MAX_PHASES; ++i) {
-        p.tile_start[i] = tiles;
-        if (i < nphase) {
-            p.ph[i] = phases[i];
-            tiles += cdiv((long)p.N * phases[i].Qh * phases[i].Qw, BM) * p.ntn;
-        }
-    }
-    p.tile_start[SCD_MAX_PHASES] = tiles;
+    if (!ring) return -1;
+    const int tiles = fill_tiles(p, nphase, phases, 256, cdiv(p.Co, 128));
     if (tiles == 0) return 0;
-    const long wb = (long)p.Co * p.wrow * esz;
-    if (xb >= (1L << 31) - 64 || wb >= (1L << 31) - 64) return SCD_ERR_ARG;   // 32-bit buffer offsets
-    p.xbytes = (int)xb;
-    p.wbytes = (int)wb;
-    hipStream_t st = (hipStream_t)stream;
-    if (ring) {
-        if (p.head_on) hipLaunchKernelGGL((conv_gemm_ring_kernel<true>), dim3(tiles), dim3(512), 0, st, p);
-        else if (p.bnbwd) hipLaunchKernelGGL((conv_gemm_ring_kernel<false, true>), dim3(tiles), dim3(512), 0, st, p);
-        else if (p.res) hipLaunchKernelGGL((conv_gemm_ring_kernel<false, false, true>), dim3(tiles), dim3(512), 0, st, p);
-        else hipLaunchKernelGGL((conv_gemm_ring_kernel<false>), dim3(tiles), dim3(512), 0, st, p);
-        SCD_RETURN_LAUNCH();
-    }
+    if (!fill_ranges(dtype, p, false)) return SCD_ERR_ARG;
+    if (p.head_on) hipLaunchKernelGGL((conv_gemm_ring_kernel<true>), dim3(tiles), dim3(512), 0, st, p);
+    else if (p.bnbwd) hipLaunchKernelGGL((conv_gemm_ring_kernel<false, true>), dim3(tiles), dim3(512), 0, st, p);
+    else if (p.res) hipLaunchKernelGGL((conv_gemm_ring_kernel<false, false, true>), dim3(tiles), dim3(512), 0, st, p);
+    else hipLaunchKernelGGL((conv_gemm_ring_kernel<false>), dim3(tiles), dim3(512), 0, st, p);
+    SCD_RETURN_LAUNCH();
+}
+
+// Every shape no other family takes: the 128 x 128 tile, 256 x 64 for narrow outputs (Co <= 64), bf16 or fp32.
+static int launch_tiled(int dtype, GemmParams& p, int nphase, const scd_gemm_phase* phases, long /*Mtot*/,
+                        hipStream_t st) {
+    const bool narrow = p.Co <= 64;
+    const int tiles = fill_tiles(p, nphase, phases, narrow ? 256 : 128, cdiv(p.Co, narrow ? 64 : 128));
+    if (tiles == 0) return 0;
+    if (!fill_ranges(dtype, p, false)) return SCD_ERR_ARG;
     if (dtype == SCD_DT_BF16) {
         if (narrow) return launch_gemm<h16, 256, 64>(p, tiles, st);
+        // intra-workgroup split K: grids of at most 1.5 tiles per CU with >= 16 K stages
         int ks = 1;
-        const int km = ksplit_mode();
-        if (km && !p.head_on) {
+        if (!p.head_on) {
             int kt = 0;
             for (int i = 0; i < nphase; ++i) kt = std::max(kt, phases[i].ntaps * (p.Ci / 64));
-            if (km == 2 || (kt >= 16 && 2 * (long)tiles <= 3L * num_cus())) ks = 2;
+            if (kt >= 16 && 2 * (long)tiles <= 3L * num_cus()) ks = 2;
         }
         return launch_gemm<h16, 128, 128>(p, tiles, st, ks);
     }
     if (dtype == SCD_DT_F32)
         return narrow ? launch_gemm<float, 256, 64>(p, tiles, st) : launch_gemm<float, 128, 128>(p, tiles, st);
     return SCD_ERR_ARG;
+}
+
+static int conv_gemm_launch(int dtype, GemmParams& p, int nphase, const scd_gemm_phase* phases, void* stream) {
+    if (nphase < 1 || nphase > SCD_MAX_PHASES) return SCD_ERR_ARG;
+    const int BK = dtype == SCD_DT_BF16 ? 64 : 32;
+    const int EPC = dtype == SCD_DT_BF16 ? 8 : 4;
+    if (p.Ci % BK != 0 || p.Co <= 0 || p.Co % EPC != 0 || p.N <= 0) return SCD_ERR_ARG;
+    p.nphase = nphase;
+    if (p.head_on && (p.Co <= 64 || p.Co != 128 * ((p.Co + 127) / 128))) return SCD_ERR_ARG;
+    long Mtot = 0;
+    for (int i = 0; i < nphase; ++i) {
+        if (phases[i].ntaps < 0 || phases[i].ntaps > SCD_MAX_TAPS) return SCD_ERR_ARG;
+        for (int t = 0; t < phases[i].ntaps; ++t)
+            if (phases[i].wt[t] < 0 || (long)(phases[i].wt[t] + 1) * p.Ci > p.wrow) return SCD_ERR_ARG;
+        Mtot += (long)p.N * phases[i].Qh * phases[i].Qw;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    int rc = launch_stream1x1(dtype, p, nphase, phases, Mtot, st);
+    if (rc < 0 && stream1x1_mode() == 2) return SCD_ERR_ARG;
+    if (rc < 0) rc = launch_heads384(dtype, p, nphase, phases, Mtot, st);
+    if (rc < 0) rc = launch_pp(dtype, p, nphase, phases, Mtot, st);
+    if (rc >= 0) return rc;
+    if (p.bnbwd && dtype != SCD_DT_BF16) return SCD_ERR_ARG;   // BN-backward sums: 16-bit epilogues (caller falls back)
+    rc = launch_l1p(dtype, p, nphase, phases, Mtot, st);
+    if (rc < 0) rc = launch_ring(dtype, p, nphase, phases, Mtot, st);
+    if (rc < 0) rc = launch_tiled(dtype, p, nphase, phases, Mtot, st);
+    return rc;
 }
 
 static void fill_params(GemmParams& p, const void* x, const void* w, void* y, const float* bias, double* stats, int N,
@@ -4181,18 +3610,8 @@ static void fill_params(GemmParams& p, const void* x, const void* w, void* y, co
     p.hid_keep = nullptr; p.hid_cols = 1 << 30;
     p.shuf = 0;
     p.stamps = scd_calib_stamp_buffer;
-    p.duo_ncu = 0; p.duo_delay = 0;
     p.res = nullptr; p.resmode = 0;
-    {
-        // read per call (tests switch them to compare the variants)
-        const char* e = getenv("SCD_HEADS_SERP");
-        p.kserp = e ? atoi(e) : 1;
-    }
-    {
-        static int dbg = -1;
-        if (dbg < 0) { const char* e = getenv("SCD_GEMM_DEBUG"); dbg = e ? atoi(e) : 0; }
-        p.debug = dbg;
-    }
+    p.kserp = heads_serp_mode();
     for (int h = 0; h < 4; ++h) { p.head_od[h] = 0; p.head_w[h] = nullptr; p.head_b[h] = nullptr; p.head_out[h] = nullptr; }
 }
 
@@ -4211,7 +3630,7 @@ extern "C" int scd_conv_gemm(int dtype, const void* x, const void* w, void* y, c
 // fp32 accumulator before the ReLU and the result is rounded once at the store (the RES instantiations of the
 // register-staged, ring and ping-pong kernels; `accumulate` adds after the ReLU and a first rounding).  res == NULL
 // runs the very kernels of scd_conv_gemm.  The row-ring kernel (forward) and the 1x1 stream kernel (mode 3) have the
-// epilogue too and take this entry point's calls with a bias, a ReLU or a residual; the duo and heads kernels do not.
+// epilogue too and take this entry point's calls with a bias, a ReLU or a residual; the heads kernels do not.
 extern "C" int scd_conv_gemm_res(int dtype, const void* x, const void* w, void* y, const float* bias, const void* res,
                                  int N, int Hi, int Wi, int Ci, int Ho, int Wo, int Co, int in_stride, int out_stride,
                                  int wrow, int relu, int nphase, const scd_gemm_phase* phases, void* stream) {
@@ -4255,9 +3674,7 @@ extern "C" int scd_conv_dgrad_s2(int dtype, const void* dy, const void* w3, void
     // forward 2x2-tap GEMM over dy whose 4 Cin output columns are the four sub-pixel phases (operand: pack mode 3);
     // only where the ping-pong kernel takes it (its epilogue stores the phases as pixels)
     const int Co = 4 * Cin;
-    const long Mtot = (long)N * Hq * Wq;
-    const int bn = pp_bn(dtype, Co);
-    if (!bn || Cin % 8 || (long)cdiv(Mtot, 256) * (Co / bn) < 256) return SCD_ERR_ARG;
+    if (!pp_tile_bn(dtype, Co, (long)N * Hq * Wq) || Cin % 8) return SCD_ERR_ARG;
     GemmParams p;
     fill_params(p, dy, w3, dx, nullptr, nullptr, N, Hq, Wq, Cg, Hq, Wq, Co, 1, 1, 4 * Cg, 0, accumulate);
     p.shuf = 1;
@@ -4298,43 +3715,45 @@ extern "C" size_t scd_conv_wgrad_workspace(int Cg, int T, int Ci, int nsplit) {
     return (size_t)nsplit * Cg * T * Ci * sizeof(float);
 }
 
-static bool wgrad_fastx() {
-    static int mode = -2;
-    if (mode == -2) { const char* e = getenv("SCD_WGRAD_FASTX"); mode = e ? atoi(e) : 1; }
-    return mode != 0;
-}
-
 static void wgrad_tile(int dtype, long M, int Cg, int& tm, int& tn) {
     (void)dtype; (void)M;
     if (Cg <= 64) { tm = 64; tn = 256; }
     else { tm = 128; tn = 128; }
 }
 
+// conv_wgrad_kernel on wgrad_tile's tile (BM = 64: 64 x 256, else 128 x 128) with stage addressing fx (FASTX; the
+// 128 x 128 tile has registers for FASTX 1 only and takes 0 for 2)
+template <typename T>
+static void launch_wgrad_tiled(int BM, int fx, dim3 grid, hipStream_t st, const WgradParams& p) {
+    if (BM == 64) {
+        if (fx == 1) hipLaunchKernelGGL((conv_wgrad_kernel<T, 64, 256, 1>), grid, dim3(256), 0, st, p);
+        else if (fx == 2) hipLaunchKernelGGL((conv_wgrad_kernel<T, 64, 256, 2>), grid, dim3(256), 0, st, p);
+        else hipLaunchKernelGGL((conv_wgrad_kernel<T, 64, 256, 0>), grid, dim3(256), 0, st, p);
+    } else {
+        if (fx == 1) hipLaunchKernelGGL((conv_wgrad_kernel<T, 128, 128, 1>), grid, dim3(256), 0, st, p);
+        else hipLaunchKernelGGL((conv_wgrad_kernel<T, 128, 128, 0>), grid, dim3(256), 0, st, p);
+    }
+}
+
 // the 64-pixel ping-pong weight gradient: bf16, a stage inside one output row, at least one 256-channel window
 static bool wgrad_use_pp2(int dtype, long M, int Ho, int Wo, int Cg) {
-    static int mode = -2;
-    if (mode == -2) { const char* e = getenv("SCD_WGRAD_PP2"); mode = e ? atoi(e) : 1; }
     // a stage = 64 pixels of one output row, or 64 / Wo whole rows (Wo = 16, 32: layer3/4, deconv1/2)
     const bool stage_ok = Wo % 64 == 0 || (Wo >= 8 && 64 % Wo == 0);
-    return mode && dtype == SCD_DT_BF16 && Cg >= 128 && stage_ok && ((long)Ho * Wo) % 64 == 0 && M >= 64 * 64;
+    return dtype == SCD_DT_BF16 && Cg >= 128 && stage_ok && ((long)Ho * Wo) % 64 == 0 && M >= 64 * 64;
 }
 
 // the layer1 weight gradient (conv_wgrad_l1_kernel): bf16, 64 -> 64 channels, 3x3 taps, stages inside one row
 static bool wgrad_use_l1(int dtype, long M, int Ho, int Wo, int Cg, int T, int Ci) {
-    static int mode = -2;
-    if (mode == -2) { const char* e = getenv("SCD_WGRAD_L1"); mode = e ? atoi(e) : 1; }
-    return mode && dtype == SCD_DT_BF16 && Cg == 64 && Ci == 64 && T == 9 && Wo % 64 == 0 && M % 64 == 0 &&
+    return dtype == SCD_DT_BF16 && Cg == 64 && Ci == 64 && T == 9 && Wo % 64 == 0 && M % 64 == 0 &&
            (long)Ho * Wo * 64 <= (1L << 30) && M >= 64;
 }
 
-// >= 16 stages per workgroup, at most 192 workgroups (SCD_WGRAD_L1_NSPLIT): in the step this kernel shares the chip
+// >= 16 stages per workgroup, at most 192 workgroups: in the step this kernel shares the chip
 // with the compute stream's last layer1 / stem kernels, and fewer splits shrink its 64 x 576 fp32 slab reduce
 // (round 4: 128 measured +1% per step against 256; round 5: 192 +0.3% against 128 in 8 of 8 A/B pairs on two boxes,
 // profiles/r5_ab.txt)
 static int wgrad_l1_nsplit(long M) {
-    static long cap = -2;
-    if (cap == -2) { const char* e = getenv("SCD_WGRAD_L1_NSPLIT"); cap = e ? atol(e) : 192; }
-    return (int)std::max(1L, std::min(cap, M / 64 / 16));
+    return (int)std::max(1L, std::min(192L, M / 64 / 16));
 }
 
 // channel window of the ping-pong weight gradient: 256 (NQ 4) or, for widths that are multiples of 192 only, 192
@@ -4344,22 +3763,15 @@ static int wgrad_pp2_win(int Cg) {
     return Cg < 256 ? 128 : 256;           // 128: NQ 2 (the heatmap head, layer2); else 256 windows + a remainder
 }
 
-// split count from a wave-quantisation cost model (SCD_WGRAD_NSMODEL=0: the fixed rules below it).  A launch of
+// split count from a wave-quantisation cost model.  A launch of
 // tiles x ns workgroups runs in ceil(tiles*ns / slots) rounds; a round costs its K stages (stage_us each) plus the
-// workgroup's fp32 slab store (epi_us), and every split adds one slab to the reduce, priced at 0.8 TB/s
-// (SCD_WGRAD_SLAB_TBPS): the reduce reads ~3.5 TB/s alone but a fraction of that inside the step, beside the compute
+// workgroup's fp32 slab store (epi_us), and every split adds one slab to the reduce, priced at 0.8 TB/s:
+// the reduce reads ~3.5 TB/s alone but a fraction of that inside the step, beside the compute
 // stream's BN passes; pricing it at 3.5 measured 1% slower per step.  Candidates are whole XCD groups (multiples of
 // 8) within the pixel and slab-memory caps.
-static bool wgrad_nsmodel() {
-    static int mode = -2;
-    if (mode == -2) { const char* e = getenv("SCD_WGRAD_NSMODEL"); mode = e ? atoi(e) : 1; }
-    return mode != 0;
-}
-
 static long wgrad_ns_model(long M, long tiles, int slots, int kp, double stage_us, double epi_us, double slab_bytes,
                            long ns_max, bool any_ns = false) {
-    static double slab_rate = -1.0;          // bytes/us at which the reduce reads the slabs (SCD_WGRAD_SLAB_TBPS)
-    if (slab_rate < 0) { const char* e = getenv("SCD_WGRAD_SLAB_TBPS"); slab_rate = (e ? atof(e) : 0.8) * 1e6; }
+    const double slab_rate = 0.8 * 1e6;      // bytes/us at which the reduce reads the slabs
     long best = 8;
     double bt = 1e30;
     const long step = any_ns ? 1 : 8;
@@ -4378,24 +3790,13 @@ static int wgrad_pp2_nsplit(long M, int Cg, int KK) {
     // >= 8 stages per split (small layers need many splits to fill the chip: layer3 has 32 K pixels)
     const long cap_px = std::max(8L, M / 512 / 8 * 8);
     const long cap_mem = std::max(8L, (256L << 20) / std::max(1L, 4L * Cg * KK) / 8 * 8);
-    if (wgrad_nsmodel()) {
-        // one workgroup per CU; a 64-pixel stage ~ 2*win*256*64 flop at ~4.3 TF/s per CU; slab win x 256 fp32
-        const double stage_us = 2.0 * win * 256 * 64 / 4.3e6;
-        const double epi_us = 4.0 * win * 256 / (5.0e6 / 256);
-        // many tiles: splits need not come in XCD groups of 8 (wgrad_block's linear map), so one round can be filled
-        // slots: the CUs the model fills (SCD_WGRAD_SLOTS, read once; A/B of leaving CUs to the compute stream)
-        static int slots = -1;
-        if (slots < 0) { const char* e = getenv("SCD_WGRAD_SLOTS"); slots = e ? std::max(8, atoi(e)) : 256; }
-        const long ns = wgrad_ns_model(M, tiles, slots, 64, stage_us, epi_us, 4.0 * Cg * KK, std::min(cap_px, cap_mem),
-                                       tiles >= 24);
-        return (int)ns;
-    }
-    // about two rounds of one-per-CU workgroups over the channel windows, whole XCD groups, >= 2048 pixels
-    // per split, fp32 slabs capped at 256 MB
-    long ns = std::max(8L, (512L / tiles + 4) / 8 * 8);
-    ns = std::min(ns, cap_px);
-    ns = std::min(ns, cap_mem);
-    return (int)ns;
+    // one workgroup per CU; a 64-pixel stage ~ 2*win*256*64 flop at ~4.3 TF/s per CU; slab win x 256 fp32
+    const double stage_us = 2.0 * win * 256 * 64 / 4.3e6;
+    const double epi_us = 4.0 * win * 256 / (5.0e6 / 256);
+    // many tiles: splits need not come in XCD groups of 8 (wgrad_block's linear map), so one round can be filled
+    const int slots = 256;       // the CUs the model fills
+    return (int)wgrad_ns_model(M, tiles, slots, 64, stage_us, epi_us, 4.0 * Cg * KK, std::min(cap_px, cap_mem),
+                               tiles >= 24);
 }
 
 extern "C" int scd_conv_wgrad_nsplit2(int dtype, long M, int Ho, int Wo, int Cg, int T, int Ci) {
@@ -4411,7 +3812,7 @@ extern "C" int scd_conv_wgrad_nsplit(int dtype, long M, int Cg, int T, int Ci) {
     wgrad_tile(dtype, M, Cg, tm, tn);
     const long tiles = (long)cdiv(Cg, tm) * cdiv((long)T * Ci, tn);
     // ~4 waves of two-per-CU workgroups over 256 CUs, >= 1024 pixels per split, fp32 slabs capped at 256 MB
-    if (wgrad_nsmodel() && M >= 8 * 1024) {
+    if (M >= 8 * 1024) {
         // 128x128: two workgroups per CU, 64x256: one (register-bound); a stage of KP pixels ~ 2*tm*tn*KP flop
         // at ~2.4 TF/s per CU; slab tm x tn fp32
         const int KP = dtype == SCD_DT_BF16 ? 64 : 32;
@@ -4483,17 +3884,9 @@ extern "C" int scd_conv_wgrad(int dtype, const void* g, const void* x, float* ws
         wgrad_tile(dtype, M, p.cgn, BM, BN);
         p.ntm = cdiv(p.cgn, BM);
         p.ntn = cdiv(p.KK, BN);
-        // stages of one row (FASTX 1, Wo % 64 == 0) or of whole rows (FASTX 2, 64 % Wo == 0; 64 x 256 tile only)
-        const int fx = !(wgrad_fastx() && ((long)Ho * Wo) % 64 == 0) ? 0 : (Wo % 64 == 0 ? 1 : 2);
-        dim3 grid(p.ntm * p.ntn * n8);
-        if (BM == 64) {
-            if (fx == 1) hipLaunchKernelGGL((conv_wgrad_kernel<h16, 64, 256, 1>), grid, dim3(256), 0, st, p);
-            else if (fx == 2) hipLaunchKernelGGL((conv_wgrad_kernel<h16, 64, 256, 2>), grid, dim3(256), 0, st, p);
-            else hipLaunchKernelGGL((conv_wgrad_kernel<h16, 64, 256, 0>), grid, dim3(256), 0, st, p);
-        } else {
-            if (fx == 1) hipLaunchKernelGGL((conv_wgrad_kernel<h16, 128, 128, 1>), grid, dim3(256), 0, st, p);
-            else hipLaunchKernelGGL((conv_wgrad_kernel<h16, 128, 128, 0>), grid, dim3(256), 0, st, p);
-        }
+        // stages of one row (FASTX 1, Wo % 64 == 0) or of whole rows (FASTX 2, 64 % Wo == 0)
+        const int fx = ((long)Ho * Wo) % 64 != 0 ? 0 : (Wo % 64 == 0 ? 1 : 2);
+        launch_wgrad_tiled<h16>(BM, fx, dim3(p.ntm * p.ntn * n8), st, p);
         SCD_RETURN_LAUNCH();
     }
     int BM, BN;
@@ -4503,34 +3896,13 @@ extern "C" int scd_conv_wgrad(int dtype, const void* g, const void* x, float* ws
     p.nsplit = nsplit;
     dim3 grid(p.ntm * p.ntn * nsplit);
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == SCD_DT_BF16 || dtype == SCD_DT_F32) {
-        // fast addressing when a stage of KP pixels stays inside one image and one row block
-        const int KP = dtype == SCD_DT_BF16 ? 64 : 32;
-        const bool fastok = wgrad_fastx() && ((long)Ho * Wo) % KP == 0 && chunk % KP == 0;
-        const int fx = !fastok ? 0 : (Wo % KP == 0 ? 1 : (KP % Wo == 0 ? 2 : 0));
-        // (the 128 x 128 tile has registers for FASTX 1 only)
-        if (dtype == SCD_DT_BF16) {
-            if (Cg <= 64) {
-                if (fx == 1) hipLaunchKernelGGL((conv_wgrad_kernel<h16, 64, 256, 1>), grid, dim3(256), 0, st, p);
-                else if (fx == 2) hipLaunchKernelGGL((conv_wgrad_kernel<h16, 64, 256, 2>), grid, dim3(256), 0, st, p);
-                else hipLaunchKernelGGL((conv_wgrad_kernel<h16, 64, 256, 0>), grid, dim3(256), 0, st, p);
-            } else {
-                if (fx == 1) hipLaunchKernelGGL((conv_wgrad_kernel<h16, 128, 128, 1>), grid, dim3(256), 0, st, p);
-                else hipLaunchKernelGGL((conv_wgrad_kernel<h16, 128, 128, 0>), grid, dim3(256), 0, st, p);
-            }
-        } else {
-            if (Cg <= 64) {
-                if (fx == 1) hipLaunchKernelGGL((conv_wgrad_kernel<float, 64, 256, 1>), grid, dim3(256), 0, st, p);
-                else if (fx == 2) hipLaunchKernelGGL((conv_wgrad_kernel<float, 64, 256, 2>), grid, dim3(256), 0, st, p);
-                else hipLaunchKernelGGL((conv_wgrad_kernel<float, 64, 256, 0>), grid, dim3(256), 0, st, p);
-            } else {
-                if (fx == 1) hipLaunchKernelGGL((conv_wgrad_kernel<float, 128, 128, 1>), grid, dim3(256), 0, st, p);
-                else hipLaunchKernelGGL((conv_wgrad_kernel<float, 128, 128, 0>), grid, dim3(256), 0, st, p);
-            }
-        }
-    } else {
-        return SCD_ERR_ARG;
-    }
+    if (dtype != SCD_DT_BF16 && dtype != SCD_DT_F32) return SCD_ERR_ARG;
+    // fast addressing when a stage of KP pixels stays inside one image and one row block
+    const int KP = dtype == SCD_DT_BF16 ? 64 : 32;
+    const bool fastok = ((long)Ho * Wo) % KP == 0 && chunk % KP == 0;
+    const int fx = !fastok ? 0 : (Wo % KP == 0 ? 1 : (KP % Wo == 0 ? 2 : 0));
+    if (dtype == SCD_DT_BF16) launch_wgrad_tiled<h16>(BM, fx, grid, st, p);
+    else launch_wgrad_tiled<float>(BM, fx, grid, st, p);
     SCD_RETURN_LAUNCH();
 }
 

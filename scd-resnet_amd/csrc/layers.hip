@@ -903,9 +903,7 @@ extern "C" int scd_stem_pool_bwd_bn(int dtype, const void* dout, const uint8_t* 
     const int E = dtype == SCD_DT_BF16 ? 8 : 4;
     if (C % E || 256 % (C / E)) return SCD_ERR_ARG;
     const long total = (long)N * H * W * (C / E);
-    static int mode = -1;
-    if (mode < 0) { const char* e = getenv("SCD_POOL_2X2"); mode = e ? atoi(e) : 1; }
-    if (mode && H == 2 * Ho && W == 2 * Wo && (long)N * H * W * C < (1L << 31)) {
+    if (H == 2 * Ho && W == 2 * Wo && (long)N * H * W * C < (1L << 31)) {
         static const int g2b = resident_grid((const void*)stem_pool_bwd_bn_2x2_kernel<h16>, 256);
         static const int g2f = resident_grid((const void*)stem_pool_bwd_bn_2x2_kernel<float>, 256);
         const long blocks2 = (long)N * Ho * Wo * (C / E);
@@ -976,18 +974,11 @@ extern "C" int scd_heads_bwd(int dtype, const void* hid, int N, int HW, int nh, 
     if (P * nh * Hd >= (1L << 31)) return SCD_ERR_ARG;     // 32-bit element offsets
     const int G = 512 / cpp;                                // pixel lanes (cpp <= 256 -> G >= 2)
     const int threads = G * cpp;
-    static int pxb_env = -1;
-    if (pxb_env < 0) { const char* e = getenv("SCD_HEADS_PXB"); pxb_env = e ? atoi(e) : 0; }
-    const int PXB = pxb_env > 0 ? pxb_env : 2048;      // one 1-per-CU round at B=32, 128x128
+    const int PXB = 2048;                              // one 1-per-CU round at B=32, 128x128
     const int blocks = cdiv(P, PXB);
     hipStream_t st = (hipStream_t)stream;
-    static int u_env = -1;
-    if (u_env < 0) { const char* e = getenv("SCD_HEADS_U"); u_env = e ? atoi(e) : 8; }
-    if (dtype == SCD_DT_BF16 && u_env == 8)
+    if (dtype == SCD_DT_BF16)
         hipLaunchKernelGGL((heads_bwd_kernel<h16, 8>), dim3(blocks), dim3(threads), 0, st, (const h16*)hid, N,
-                           HW, d, (h16*)dhid, acc, accsz, PXB);
-    else if (dtype == SCD_DT_BF16)
-        hipLaunchKernelGGL((heads_bwd_kernel<h16, 4>), dim3(blocks), dim3(threads), 0, st, (const h16*)hid, N,
                            HW, d, (h16*)dhid, acc, accsz, PXB);
     else if (dtype == SCD_DT_F32)
         hipLaunchKernelGGL((heads_bwd_kernel<float, 4>), dim3(blocks), dim3(threads), 0, st, (const float*)hid, N, HW,
@@ -1067,9 +1058,7 @@ extern "C" int scd_heads_bwd_packed_split(int dtype, const void* hid, int N, int
     d.pk = packed;
     const int G = 512 / cpp;
     const int threads = G * cpp;
-    static int pxb_env = -1;
-    if (pxb_env < 0) { const char* ev = getenv("SCD_HEADS_PXB"); pxb_env = ev ? atoi(ev) : 0; }
-    const int PXB = pxb_env > 0 ? pxb_env : 2048;
+    const int PXB = 2048;
     const int blocks = cdiv(P, PXB);
     if (dtype == SCD_DT_BF16)
         hipLaunchKernelGGL((heads_bwd_kernel<h16, 8, true>), dim3(blocks), dim3(threads), 0, st, (const h16*)hid,

