@@ -26,109 +26,6 @@
 namespace {
 SCD_KERNEL_NS_BEGIN
 
-// sum replicas into replica 0 and zero the others (buffers are persistent: the consumer re-zeroes)
-__global__ void stats_collapse_kernel(double* stats, int nrep, int n) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    double s = 0.0;
-    for (int r = 0; r < nrep; ++r) {
-        s += stats[(long)r * n + i];
-        if (r) stats[(long)r * n + i] = 0.0;
-    }
-    stats[i] = s;
-}
-
-// SyncBN staging: out[i] = sum of the replicas, every replica zeroed (two layers' sums side by side in one buffer,
-// so one collective reduces both)
-__global__ void stats_collapse_to_kernel(double* stats, int nrep, int n, double* out) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    double s = 0.0;
-    for (int r = 0; r < nrep; ++r) {
-        s += stats[(long)r * n + i];
-        stats[(long)r * n + i] = 0.0;
-    }
-    out[i] = s;
-}
-
-// one wave per channel: lane r sums replica r (and zeroes it: persistent, consumer-cleared buffers)
-__device__ __forceinline__ void wave_collect(double* stats, int nrep, int C, int c, double& s, double& q) {
-    const int lane = threadIdx.x & 63;
-    double a = 0.0, b = 0.0;
-    for (int r = lane; r < nrep; r += 64) {
-        double* p = stats + (long)r * 2 * C;
-        a += p[c];
-        b += p[C + c];
-        p[c] = 0.0;
-        p[C + c] = 0.0;
-    }
-    s = wave_sum_d(a);
-    q = wave_sum_d(b);
-}
-
-__device__ __forceinline__ void bn_finalize_channel(int c, double* stats, int nrep, int C, double count,
-                                                    const float* gamma, const float* beta, float* rmean, float* rvar,
-                                                    float momentum, float eps, float* mean_o, float* invstd_o,
-                                                    float* scale_o, float* shift_o, int64_t* nbt) {
-    double mean, var;
-    if (stats) {
-        double s, q;
-        wave_collect(stats, nrep, C, c, s, q);
-        mean = s / count;
-        var = q / count - mean * mean;
-        if (var < 0.0) var = 0.0;
-    } else {                       // eval mode: normalise with the running statistics
-        mean = rmean[c];
-        var = rvar[c];
-    }
-    if ((threadIdx.x & 63) != 0) return;
-    const float invstd = (float)(1.0 / sqrt(var + (double)eps));
-    const float g = gamma ? gamma[c] : 1.f;
-    const float b = beta ? beta[c] : 0.f;
-    const float sc = g * invstd;
-    mean_o[c] = (float)mean;
-    invstd_o[c] = invstd;
-    scale_o[c] = sc;
-    shift_o[c] = b - (float)mean * sc;
-    // (statistics that are NaN -- a failed peer-memory SyncBN all-reduce poisons its result, scdhip/peer.py -- leave the
-    // running statistics AND num_batches_tracked as they were, so a checkpoint written after the failure still carries
-    // the last good, mutually consistent ones; channel 0's lane counts the batch)
-    if (c == 0 && nbt && stats && mean == mean && var == var) *nbt += 1;
-    if (stats && rmean && mean == mean && var == var) {
-        const double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
-        rmean[c] = (1.f - momentum) * rmean[c] + momentum * (float)mean;
-        rvar[c] = (1.f - momentum) * rvar[c] + momentum * (float)unbiased;
-    }
-}
-
-__global__ void bn_finalize_kernel(double* stats, int nrep, int C, double count, const float* gamma,
-                                   const float* beta, float* rmean, float* rvar, int64_t* nbt, float momentum,
-                                   float eps, float* mean_o, float* invstd_o, float* scale_o, float* shift_o) {
-    const int c = blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
-    if (c >= C) return;
-    bn_finalize_channel(c, stats, nrep, C, count, gamma, beta, rmean, rvar, momentum, eps, mean_o, invstd_o, scale_o,
-                        shift_o, nbt);
-}
-
-// up to SCD_BN_FIN_MAX layers in one launch (scd_bn_finalize_n): layer i owns blocks [b0[i], b0[i + 1])
-struct FinN {
-    scd_bn_fin_args l[SCD_BN_FIN_MAX];
-    int b0[SCD_BN_FIN_MAX + 1];
-    int n;
-};
-__global__ void bn_finalize_n_kernel(FinN f) {
-    int i = 0;
-#pragma unroll
-    for (int k = 1; k < SCD_BN_FIN_MAX; ++k)
-        if (k < f.n && (int)blockIdx.x >= f.b0[k]) i = k;
-    const scd_bn_fin_args& a = f.l[i];
-    const int blk = blockIdx.x - f.b0[i];
-    const int c = blk * (blockDim.x / 64) + (threadIdx.x >> 6);
-    if (c >= a.C) return;
-    bn_finalize_channel(c, a.stats, a.nrep, a.C, a.count, a.gamma, a.beta, a.running_mean, a.running_var, a.momentum,
-                        a.eps, a.mean, a.invstd, a.scale, a.shift, a.num_batches);
-}
-
 // E consecutive per-channel floats (E = 4 or 8, 16-B aligned) as float4 loads
 template <int E>
 __device__ __forceinline__ void load_params(const float* p, float* v) {
@@ -312,50 +209,6 @@ __global__ __launch_bounds__(256, BN_EW_WAVES) void bn_bwd_reduce_kernel(const T
         atomic_add_f64(stats + ((long)rep * 2 + 0) * ld + c, ss);
         atomic_add_f64(stats + ((long)rep * 2 + 1) * ld + c, qq);
     }
-}
-
-__device__ __forceinline__ void bn_bwd_finalize_channel(int c, double* stats, int nrep, int C, double count,
-                                                        const float* gamma, const float* mean, const float* invstd,
-                                                        float* dgamma, float* dbeta, float gscale, float* coef) {
-    double s, q;
-    wave_collect(stats, nrep, C, c, s, q);
-    if ((threadIdx.x & 63) != 0) return;
-    if (dgamma) dgamma[c] += gscale * (float)q;
-    if (dbeta) dbeta[c] += gscale * (float)s;
-    const float g = gamma ? gamma[c] : 1.f;
-    const float is = invstd[c];
-    const float sc = g * is;
-    const float k1 = (float)(s / count);
-    const float k2 = (float)(q / count);
-    // dy = sc*(dz - k1 - xhat*k2), xhat = (y-mean)*is
-    coef[c] = sc;
-    coef[C + c] = -sc * is * k2;
-    coef[2 * C + c] = -sc * k1 + sc * is * k2 * mean[c];
-}
-
-__global__ void bn_bwd_finalize_kernel(double* stats, int nrep, int C, double count, const float* gamma,
-                                       const float* mean, const float* invstd, float* dgamma, float* dbeta,
-                                       float gscale, float* coef) {
-    const int c = blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
-    if (c >= C) return;
-    bn_bwd_finalize_channel(c, stats, nrep, C, count, gamma, mean, invstd, dgamma, dbeta, gscale, coef);
-}
-
-struct BwdFinN {
-    scd_bn_bwd_fin_args l[SCD_BN_FIN_MAX];
-    int b0[SCD_BN_FIN_MAX + 1];
-    int n;
-};
-__global__ void bn_bwd_finalize_n_kernel(BwdFinN f) {
-    int i = 0;
-#pragma unroll
-    for (int k = 1; k < SCD_BN_FIN_MAX; ++k)
-        if (k < f.n && (int)blockIdx.x >= f.b0[k]) i = k;
-    const scd_bn_bwd_fin_args& a = f.l[i];
-    const int c = (blockIdx.x - f.b0[i]) * (blockDim.x / 64) + (threadIdx.x >> 6);
-    if (c >= a.C) return;
-    bn_bwd_finalize_channel(c, a.stats, a.nrep, a.C, a.count, a.gamma, a.mean, a.invstd, a.dgamma, a.dbeta, a.gscale,
-                            a.coef);
 }
 
 template <typename T>
@@ -595,20 +448,293 @@ inline int ew_grid(int resident, long nvec, int cpr) {
     g = std::max<long>(m, g / m * m);
     return (int)g;
 }
-inline int fin_blocks(int C) { return (C + 3) / 4; }   // 4 waves (channels) per 256-thread block
 // dynamic LDS of an elementwise backward kernel staging nsrc per-channel arrays over its channel window (chan_window)
 inline size_t ew_param_lds(int nsrc, int C, int E) { return (size_t)nsrc * std::min(C, 256 * E) * sizeof(float); }
 constexpr size_t EW_LDS_MAX = 64 * 1024;
-// resident blocks of `kernel` with `lds` bytes of dynamic LDS, cached per (kernel slot, window width)
-template <int SLOT>
-inline int ew_resident(const void* kernel, size_t lds) {
+// resident blocks of Kernel with `lds` bytes of dynamic LDS, cached per kernel and window width
+template <auto Kernel>
+inline int ew_resident(size_t lds) {
     static int cache[EW_LDS_MAX / 16 + 1] = {0};        // lds is a multiple of 16 B (E >= 4 floats per chunk)
     const size_t k = std::min<size_t>(lds / 16, EW_LDS_MAX / 16);
-    if (!cache[k]) cache[k] = resident_grid(kernel, 256, lds);
+    if (!cache[k]) cache[k] = resident_grid((const void*)Kernel, 256, lds);
     return cache[k];
 }
 
 SCD_KERNEL_NS_END
+}  // namespace
+
+extern "C" int scd_bn_apply(int dtype, const void* y, void* out, int C, long total, const float* scale,
+                            const float* shift, const void* res, const float* rscale, const float* rshift, int relu,
+                            void* stream) {
+    SCD_F16_FWD(scd_bn_apply, y, out, C, total, scale, shift, res, rscale, rshift, relu, stream);
+    return scd_dispatch_dtype(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        constexpr int E = 16 / sizeof(T);
+        if (C % E || !ew_rows_ok(C / E)) return SCD_ERR_ARG;
+        long nvec = total / E;
+        static const int g = resident_grid((const void*)bn_apply_kernel<T>, 256);
+        hipLaunchKernelGGL((bn_apply_kernel<T>), dim3(ew_grid(g, nvec, C / E)), dim3(256), 0, (hipStream_t)stream,
+                           (const T*)y, (T*)out, C, (unsigned)nvec, scale, shift, (const T*)res, rscale, rshift, relu);
+        SCD_RETURN_LAUNCH();
+    });
+}
+
+extern "C" int scd_bn_bwd_reduce(int dtype, const void* dout, const void* mask, const void* y, const float* relu_scale,
+                                 const float* relu_shift, const float* mean,
+                                 const float* invstd, int C, long total, double* stats, void* stream) {
+    SCD_F16_FWD(scd_bn_bwd_reduce, dout, mask, y, relu_scale, relu_shift, mean, invstd, C, total, stats, stream);
+    return scd_dispatch_dtype(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        constexpr int E = 16 / sizeof(T);
+        if (C % E) return SCD_ERR_ARG;
+        const long rows = total / C;
+        const int cpr = C / E;
+        // rows wider than 256 chunks run as channel slices of 256 chunks (ld = the full row)
+        if (!ew_rows_ok(cpr) || total >= (1L << 31)) return SCD_ERR_ARG;
+        const int scpr = std::min(cpr, 256), sC = scpr * E;
+        // one round of resident blocks (at most), at least 8 rows per row lane
+        const long nb = ew_resident<bn_bwd_reduce_kernel<T>>((size_t)4 * sC * sizeof(float));
+        const long rpi = 256 / scpr;
+        const long rpb = std::max<long>(8 * rpi, (rows + nb - 1) / nb + rpi - 1) / rpi * rpi;
+        const int blocks = cdiv(rows, rpb);
+        for (int c0 = 0; c0 < C; c0 += sC) {
+            const T* mk = mask ? (const T*)mask + c0 : nullptr;
+            const float* rs = relu_scale ? relu_scale + c0 : nullptr;
+            const float* rh = relu_shift ? relu_shift + c0 : nullptr;
+            hipLaunchKernelGGL((bn_bwd_reduce_kernel<T>), dim3(blocks), dim3(256), 4 * sC * 4, (hipStream_t)stream,
+                               (const T*)dout + c0, mk, (const T*)y + c0, rs, rh, mean + c0, invstd + c0, sC, C,
+                               (unsigned)rows, (unsigned)rpb, stats + c0);
+            hipError_t e = hipGetLastError();
+            if (e != hipSuccess) return (int)e;
+        }
+        return 0;
+    });
+}
+
+extern "C" int scd_bn_bwd_reduce2(int dtype, const void* dout, const void* mask, const void* ya, const void* yb,
+                                  const float* mean_a, const float* invstd_a, const float* mean_b,
+                                  const float* invstd_b, int C, long total, double* stats_a, double* stats_b,
+                                  void* stream) {
+    SCD_F16_FWD(scd_bn_bwd_reduce2, dout, mask, ya, yb, mean_a, invstd_a, mean_b, invstd_b, C, total, stats_a, stats_b,
+                stream);
+    return scd_dispatch_dtype(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        constexpr int E = 16 / sizeof(T);
+        if (!dout || !mask || !ya || !yb || C % E) return SCD_ERR_ARG;
+        const long rows = total / C;
+        const int cpr = C / E;
+        if (!ew_rows_ok(cpr) || total >= (1L << 31)) return SCD_ERR_ARG;
+        const int scpr = std::min(cpr, 256), sC = scpr * E;
+        // the same row partition as scd_bn_bwd_reduce (per-thread partial sums identical to two separate passes)
+        const long nb = ew_resident<bn_bwd_reduce_kernel<T>>((size_t)4 * sC * sizeof(float));
+        const long rpi = 256 / scpr;
+        const long rpb = std::max<long>(8 * rpi, (rows + nb - 1) / nb + rpi - 1) / rpi * rpi;
+        const int blocks = cdiv(rows, rpb);
+        for (int c0 = 0; c0 < C; c0 += sC) {
+            hipLaunchKernelGGL((bn_bwd_reduce2_kernel<T>), dim3(blocks), dim3(256), 4 * sC * 4, (hipStream_t)stream,
+                               (const T*)dout + c0, (const T*)mask + c0, (const T*)ya + c0, (const T*)yb + c0,
+                               mean_a + c0, invstd_a + c0, mean_b + c0, invstd_b + c0, sC, C, (unsigned)rows,
+                               (unsigned)rpb, stats_a + c0, stats_b + c0);
+            hipError_t e = hipGetLastError();
+            if (e != hipSuccess) return (int)e;
+        }
+        return 0;
+    });
+}
+
+extern "C" int scd_bn_bwd_apply2(int dtype, const void* dout, const void* mask, const void* ya, const void* yb,
+                                 const float* coef_a, const float* coef_b, int C, long total, void* dya, void* dyb,
+                                 void* stream) {
+    SCD_F16_FWD(scd_bn_bwd_apply2, dout, mask, ya, yb, coef_a, coef_b, C, total, dya, dyb, stream);
+    return scd_dispatch_dtype(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        constexpr int E = 16 / sizeof(T);
+        if (!dout || !mask || !ya || !yb || !dya || !dyb || C % E || !ew_rows_ok(C / E) || total / E >= (1L << 32))
+            return SCD_ERR_ARG;
+        const long nvec = total / E;
+        const size_t lds = ew_param_lds(6, C, E);
+        if (lds > EW_LDS_MAX) return SCD_ERR_ARG;
+        const int g = ew_resident<bn_bwd_apply2_kernel<T>>(lds);
+        hipLaunchKernelGGL((bn_bwd_apply2_kernel<T>), dim3(ew_grid(g, nvec, C / E)), dim3(256), lds,
+                           (hipStream_t)stream, (const T*)dout, (const T*)mask, (const T*)ya, (const T*)yb, coef_a,
+                           coef_b, C, (unsigned)nvec, (T*)dya, (T*)dyb);
+        SCD_RETURN_LAUNCH();
+    });
+}
+
+extern "C" int scd_bn_bwd_apply(int dtype, const void* dout, const void* mask, const void* y, const float* relu_scale,
+                                const float* relu_shift, const float* coef, int C, long total, void* dy, void* dz,
+                                void* stream) {
+    SCD_F16_FWD(scd_bn_bwd_apply, dout, mask, y, relu_scale, relu_shift, coef, C, total, dy, dz, stream);
+    return scd_dispatch_dtype(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        constexpr int E = 16 / sizeof(T);
+        if (C % E || !ew_rows_ok(C / E)) return SCD_ERR_ARG;
+        long nvec = total / E;
+        const size_t lds = ew_param_lds(5, C, E);
+        if (lds > EW_LDS_MAX) return SCD_ERR_ARG;
+        const int g = ew_resident<bn_bwd_apply_kernel<T>>(lds);
+        hipLaunchKernelGGL((bn_bwd_apply_kernel<T>), dim3(ew_grid(g, nvec, C / E)), dim3(256), lds,
+                           (hipStream_t)stream, (const T*)dout, (const T*)mask, (const T*)y, relu_scale, relu_shift,
+                           coef, C, (unsigned)nvec, (T*)dy, (T*)dz);
+        SCD_RETURN_LAUNCH();
+    });
+}
+
+// ---------------------------------------------------------------- statistics: collapse and finalize (no dtype)
+// fp64 sums in, fp32 per-channel parameters out: the first build alone holds these entry points and their kernels.
+#ifndef SCD_F16_BUILD
+namespace {
+
+// sum replicas into replica 0 and zero the others (buffers are persistent: the consumer re-zeroes)
+__global__ void stats_collapse_kernel(double* stats, int nrep, int n) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    double s = 0.0;
+    for (int r = 0; r < nrep; ++r) {
+        s += stats[(long)r * n + i];
+        if (r) stats[(long)r * n + i] = 0.0;
+    }
+    stats[i] = s;
+}
+
+// SyncBN staging: out[i] = sum of the replicas, every replica zeroed (two layers' sums side by side in one buffer,
+// so one collective reduces both)
+__global__ void stats_collapse_to_kernel(double* stats, int nrep, int n, double* out) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    double s = 0.0;
+    for (int r = 0; r < nrep; ++r) {
+        s += stats[(long)r * n + i];
+        stats[(long)r * n + i] = 0.0;
+    }
+    out[i] = s;
+}
+
+// one wave per channel: lane r sums replica r (and zeroes it: persistent, consumer-cleared buffers)
+__device__ __forceinline__ void wave_collect(double* stats, int nrep, int C, int c, double& s, double& q) {
+    const int lane = threadIdx.x & 63;
+    double a = 0.0, b = 0.0;
+    for (int r = lane; r < nrep; r += 64) {
+        double* p = stats + (long)r * 2 * C;
+        a += p[c];
+        b += p[C + c];
+        p[c] = 0.0;
+        p[C + c] = 0.0;
+    }
+    s = wave_sum_d(a);
+    q = wave_sum_d(b);
+}
+
+__device__ __forceinline__ void bn_finalize_channel(int c, double* stats, int nrep, int C, double count,
+                                                    const float* gamma, const float* beta, float* rmean, float* rvar,
+                                                    float momentum, float eps, float* mean_o, float* invstd_o,
+                                                    float* scale_o, float* shift_o, int64_t* nbt) {
+    double mean, var;
+    if (stats) {
+        double s, q;
+        wave_collect(stats, nrep, C, c, s, q);
+        mean = s / count;
+        var = q / count - mean * mean;
+        if (var < 0.0) var = 0.0;
+    } else {                       // eval mode: normalise with the running statistics
+        mean = rmean[c];
+        var = rvar[c];
+    }
+    if ((threadIdx.x & 63) != 0) return;
+    const float invstd = (float)(1.0 / sqrt(var + (double)eps));
+    const float g = gamma ? gamma[c] : 1.f;
+    const float b = beta ? beta[c] : 0.f;
+    const float sc = g * invstd;
+    mean_o[c] = (float)mean;
+    invstd_o[c] = invstd;
+    scale_o[c] = sc;
+    shift_o[c] = b - (float)mean * sc;
+    // (statistics that are NaN -- a failed peer-memory SyncBN all-reduce poisons its result, scdhip/peer.py -- leave the
+    // running statistics AND num_batches_tracked as they were, so a checkpoint written after the failure still carries
+    // the last good, mutually consistent ones; channel 0's lane counts the batch)
+    if (c == 0 && nbt && stats && mean == mean && var == var) *nbt += 1;
+    if (stats && rmean && mean == mean && var == var) {
+        const double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
+        rmean[c] = (1.f - momentum) * rmean[c] + momentum * (float)mean;
+        rvar[c] = (1.f - momentum) * rvar[c] + momentum * (float)unbiased;
+    }
+}
+
+__global__ void bn_finalize_kernel(double* stats, int nrep, int C, double count, const float* gamma,
+                                   const float* beta, float* rmean, float* rvar, int64_t* nbt, float momentum,
+                                   float eps, float* mean_o, float* invstd_o, float* scale_o, float* shift_o) {
+    const int c = blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
+    if (c >= C) return;
+    bn_finalize_channel(c, stats, nrep, C, count, gamma, beta, rmean, rvar, momentum, eps, mean_o, invstd_o, scale_o,
+                        shift_o, nbt);
+}
+
+// up to SCD_BN_FIN_MAX layers in one launch (scd_bn_finalize_n): layer i owns blocks [b0[i], b0[i + 1])
+struct FinN {
+    scd_bn_fin_args l[SCD_BN_FIN_MAX];
+    int b0[SCD_BN_FIN_MAX + 1];
+    int n;
+};
+__global__ void bn_finalize_n_kernel(FinN f) {
+    int i = 0;
+#pragma unroll
+    for (int k = 1; k < SCD_BN_FIN_MAX; ++k)
+        if (k < f.n && (int)blockIdx.x >= f.b0[k]) i = k;
+    const scd_bn_fin_args& a = f.l[i];
+    const int blk = blockIdx.x - f.b0[i];
+    const int c = blk * (blockDim.x / 64) + (threadIdx.x >> 6);
+    if (c >= a.C) return;
+    bn_finalize_channel(c, a.stats, a.nrep, a.C, a.count, a.gamma, a.beta, a.running_mean, a.running_var, a.momentum,
+                        a.eps, a.mean, a.invstd, a.scale, a.shift, a.num_batches);
+}
+
+__device__ __forceinline__ void bn_bwd_finalize_channel(int c, double* stats, int nrep, int C, double count,
+                                                        const float* gamma, const float* mean, const float* invstd,
+                                                        float* dgamma, float* dbeta, float gscale, float* coef) {
+    double s, q;
+    wave_collect(stats, nrep, C, c, s, q);
+    if ((threadIdx.x & 63) != 0) return;
+    if (dgamma) dgamma[c] += gscale * (float)q;
+    if (dbeta) dbeta[c] += gscale * (float)s;
+    const float g = gamma ? gamma[c] : 1.f;
+    const float is = invstd[c];
+    const float sc = g * is;
+    const float k1 = (float)(s / count);
+    const float k2 = (float)(q / count);
+    // dy = sc*(dz - k1 - xhat*k2), xhat = (y-mean)*is
+    coef[c] = sc;
+    coef[C + c] = -sc * is * k2;
+    coef[2 * C + c] = -sc * k1 + sc * is * k2 * mean[c];
+}
+
+__global__ void bn_bwd_finalize_kernel(double* stats, int nrep, int C, double count, const float* gamma,
+                                       const float* mean, const float* invstd, float* dgamma, float* dbeta,
+                                       float gscale, float* coef) {
+    const int c = blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
+    if (c >= C) return;
+    bn_bwd_finalize_channel(c, stats, nrep, C, count, gamma, mean, invstd, dgamma, dbeta, gscale, coef);
+}
+
+struct BwdFinN {
+    scd_bn_bwd_fin_args l[SCD_BN_FIN_MAX];
+    int b0[SCD_BN_FIN_MAX + 1];
+    int n;
+};
+__global__ void bn_bwd_finalize_n_kernel(BwdFinN f) {
+    int i = 0;
+#pragma unroll
+    for (int k = 1; k < SCD_BN_FIN_MAX; ++k)
+        if (k < f.n && (int)blockIdx.x >= f.b0[k]) i = k;
+    const scd_bn_bwd_fin_args& a = f.l[i];
+    const int c = (blockIdx.x - f.b0[i]) * (blockDim.x / 64) + (threadIdx.x >> 6);
+    if (c >= a.C) return;
+    bn_bwd_finalize_channel(c, a.stats, a.nrep, a.C, a.count, a.gamma, a.mean, a.invstd, a.dgamma, a.dbeta, a.gscale,
+                            a.coef);
+}
+
+inline int fin_blocks(int C) { return (C + 3) / 4; }   // 4 waves (channels) per 256-thread block
+
 }  // namespace
 
 extern "C" int scd_stats_collapse(double* stats, int nrep, int C, void* stream) {
@@ -670,143 +796,6 @@ extern "C" int scd_bn_bwd_finalize_n(const scd_bn_bwd_fin_args* layers, int n, v
     SCD_RETURN_LAUNCH();
 }
 
-extern "C" int scd_bn_apply(int dtype, const void* y, void* out, int C, long total, const float* scale,
-                            const float* shift, const void* res, const float* rscale, const float* rshift, int relu,
-                            void* stream) {
-    SCD_F16_FWD(scd_bn_apply, y, out, C, total, scale, shift, res, rscale, rshift, relu, stream);
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == SCD_DT_BF16) {
-        if (C % 8 || !ew_rows_ok(C / 8)) return SCD_ERR_ARG;
-        long nvec = total / 8;
-        static const int g = resident_grid((const void*)bn_apply_kernel<h16>, 256);
-        hipLaunchKernelGGL((bn_apply_kernel<h16>), dim3(ew_grid(g, nvec, C / 8)), dim3(256), 0, st, (const h16*)y,
-                           (h16*)out, C, (unsigned)nvec, scale, shift, (const h16*)res, rscale, rshift, relu);
-    } else if (dtype == SCD_DT_F32) {
-        if (C % 4 || !ew_rows_ok(C / 4)) return SCD_ERR_ARG;
-        long nvec = total / 4;
-        static const int g = resident_grid((const void*)bn_apply_kernel<float>, 256);
-        hipLaunchKernelGGL((bn_apply_kernel<float>), dim3(ew_grid(g, nvec, C / 4)), dim3(256), 0, st, (const float*)y,
-                           (float*)out, C, (unsigned)nvec, scale, shift, (const float*)res, rscale, rshift, relu);
-    } else {
-        return SCD_ERR_ARG;
-    }
-    SCD_RETURN_LAUNCH();
-}
-
-extern "C" int scd_bn_bwd_reduce(int dtype, const void* dout, const void* mask, const void* y, const float* relu_scale,
-                                 const float* relu_shift, const float* mean,
-                                 const float* invstd, int C, long total, double* stats, void* stream) {
-    SCD_F16_FWD(scd_bn_bwd_reduce, dout, mask, y, relu_scale, relu_shift, mean, invstd, C, total, stats, stream);
-    hipStream_t st = (hipStream_t)stream;
-    const int E = dtype == SCD_DT_BF16 ? 8 : 4;
-    if (C % E) return SCD_ERR_ARG;
-    const long rows = total / C;
-    const int cpr = C / E;
-    // rows wider than 256 chunks run as channel slices of 256 chunks (ld = the full row)
-    if (!ew_rows_ok(cpr) || total >= (1L << 31)) return SCD_ERR_ARG;
-    const int scpr = std::min(cpr, 256), sC = scpr * E;
-    // one round of resident blocks (at most), at least 8 rows per row lane
-    const size_t lds = (size_t)4 * sC * sizeof(float);
-    const long nb = dtype == SCD_DT_BF16 ? ew_resident<4>((const void*)bn_bwd_reduce_kernel<h16>, lds)
-                                         : ew_resident<5>((const void*)bn_bwd_reduce_kernel<float>, lds);
-    const long rpi = 256 / scpr;
-    const long rpb = std::max<long>(8 * rpi, (rows + nb - 1) / nb + rpi - 1) / rpi * rpi;
-    const int blocks = cdiv(rows, rpb);
-    const int esz = dtype == SCD_DT_BF16 ? 2 : 4;
-    for (int c0 = 0; c0 < C; c0 += sC) {
-        const char* dz = (const char*)dout + (size_t)c0 * esz;
-        const char* mk = mask ? (const char*)mask + (size_t)c0 * esz : nullptr;
-        const char* yy = (const char*)y + (size_t)c0 * esz;
-        const float* rs = relu_scale ? relu_scale + c0 : nullptr;
-        const float* rh = relu_shift ? relu_shift + c0 : nullptr;
-        if (dtype == SCD_DT_BF16)
-            hipLaunchKernelGGL((bn_bwd_reduce_kernel<h16>), dim3(blocks), dim3(256), 4 * sC * 4, st, (const h16*)dz,
-                               (const h16*)mk, (const h16*)yy, rs, rh, mean + c0, invstd + c0, sC, C,
-                               (unsigned)rows, (unsigned)rpb, stats + c0);
-        else if (dtype == SCD_DT_F32)
-            hipLaunchKernelGGL((bn_bwd_reduce_kernel<float>), dim3(blocks), dim3(256), 4 * sC * 4, st, (const float*)dz,
-                               (const float*)mk, (const float*)yy, rs, rh, mean + c0, invstd + c0, sC, C,
-                               (unsigned)rows, (unsigned)rpb, stats + c0);
-        else
-            return SCD_ERR_ARG;
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return (int)e;
-    }
-    return 0;
-}
-
-extern "C" int scd_bn_bwd_reduce2(int dtype, const void* dout, const void* mask, const void* ya, const void* yb,
-                                  const float* mean_a, const float* invstd_a, const float* mean_b,
-                                  const float* invstd_b, int C, long total, double* stats_a, double* stats_b,
-                                  void* stream) {
-    SCD_F16_FWD(scd_bn_bwd_reduce2, dout, mask, ya, yb, mean_a, invstd_a, mean_b, invstd_b, C, total, stats_a, stats_b,
-                stream);
-    hipStream_t st = (hipStream_t)stream;
-    const int E = dtype == SCD_DT_BF16 ? 8 : 4;
-    if (!dout || !mask || !ya || !yb || C % E) return SCD_ERR_ARG;
-    const long rows = total / C;
-    const int cpr = C / E;
-    if (!ew_rows_ok(cpr) || total >= (1L << 31)) return SCD_ERR_ARG;
-    const int scpr = std::min(cpr, 256), sC = scpr * E;
-    // the same row partition as scd_bn_bwd_reduce (per-thread partial sums identical to two separate passes)
-    const size_t lds = (size_t)4 * sC * sizeof(float);
-    const long nb = dtype == SCD_DT_BF16 ? ew_resident<4>((const void*)bn_bwd_reduce_kernel<h16>, lds)
-                                         : ew_resident<5>((const void*)bn_bwd_reduce_kernel<float>, lds);
-    const long rpi = 256 / scpr;
-    const long rpb = std::max<long>(8 * rpi, (rows + nb - 1) / nb + rpi - 1) / rpi * rpi;
-    const int blocks = cdiv(rows, rpb);
-    const int esz = dtype == SCD_DT_BF16 ? 2 : 4;
-    for (int c0 = 0; c0 < C; c0 += sC) {
-        const size_t o = (size_t)c0 * esz;
-        const char *d = (const char*)dout + o, *m = (const char*)mask + o, *a = (const char*)ya + o,
-                   *b = (const char*)yb + o;
-        if (dtype == SCD_DT_BF16)
-            hipLaunchKernelGGL((bn_bwd_reduce2_kernel<h16>), dim3(blocks), dim3(256), 4 * sC * 4, st, (const h16*)d,
-                               (const h16*)m, (const h16*)a, (const h16*)b, mean_a + c0, invstd_a + c0,
-                               mean_b + c0, invstd_b + c0, sC, C, (unsigned)rows, (unsigned)rpb, stats_a + c0,
-                               stats_b + c0);
-        else if (dtype == SCD_DT_F32)
-            hipLaunchKernelGGL((bn_bwd_reduce2_kernel<float>), dim3(blocks), dim3(256), 4 * sC * 4, st, (const float*)d,
-                               (const float*)m, (const float*)a, (const float*)b, mean_a + c0, invstd_a + c0,
-                               mean_b + c0, invstd_b + c0, sC, C, (unsigned)rows, (unsigned)rpb, stats_a + c0,
-                               stats_b + c0);
-        else
-            return SCD_ERR_ARG;
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return (int)e;
-    }
-    return 0;
-}
-
-extern "C" int scd_bn_bwd_apply2(int dtype, const void* dout, const void* mask, const void* ya, const void* yb,
-                                 const float* coef_a, const float* coef_b, int C, long total, void* dya, void* dyb,
-                                 void* stream) {
-    SCD_F16_FWD(scd_bn_bwd_apply2, dout, mask, ya, yb, coef_a, coef_b, C, total, dya, dyb, stream);
-    hipStream_t st = (hipStream_t)stream;
-    const int E = dtype == SCD_DT_BF16 ? 8 : 4;
-    if (!dout || !mask || !ya || !yb || !dya || !dyb || C % E || !ew_rows_ok(C / E) || total / E >= (1L << 32))
-        return SCD_ERR_ARG;
-    const long nvec = total / E;
-    if (dtype == SCD_DT_BF16) {
-        const size_t lds = ew_param_lds(6, C, 8);
-        if (lds > EW_LDS_MAX) return SCD_ERR_ARG;
-        const int g = ew_resident<0>((const void*)bn_bwd_apply2_kernel<h16>, lds);
-        hipLaunchKernelGGL((bn_bwd_apply2_kernel<h16>), dim3(ew_grid(g, nvec, C / 8)), dim3(256), lds, st,
-                           (const h16*)dout, (const h16*)mask, (const h16*)ya, (const h16*)yb, coef_a,
-                           coef_b, C, (unsigned)nvec, (h16*)dya, (h16*)dyb);
-    } else if (dtype == SCD_DT_F32) {
-        const size_t lds = ew_param_lds(6, C, 4);
-        if (lds > EW_LDS_MAX) return SCD_ERR_ARG;
-        const int g = ew_resident<1>((const void*)bn_bwd_apply2_kernel<float>, lds);
-        hipLaunchKernelGGL((bn_bwd_apply2_kernel<float>), dim3(ew_grid(g, nvec, C / 4)), dim3(256), lds, st,
-                           (const float*)dout, (const float*)mask, (const float*)ya, (const float*)yb, coef_a, coef_b,
-                           C, (unsigned)nvec, (float*)dya, (float*)dyb);
-    } else {
-        return SCD_ERR_ARG;
-    }
-    SCD_RETURN_LAUNCH();
-}
-
 extern "C" int scd_bn_bwd_finalize(double* stats, int nrep, int C, double count, const float* gamma,
                                    const float* mean, const float* invstd, float* dgamma, float* dbeta, float gscale,
                                    float* coef, void* stream) {
@@ -814,32 +803,4 @@ extern "C" int scd_bn_bwd_finalize(double* stats, int nrep, int C, double count,
                        count, gamma, mean, invstd, dgamma, dbeta, gscale, coef);
     SCD_RETURN_LAUNCH();
 }
-
-extern "C" int scd_bn_bwd_apply(int dtype, const void* dout, const void* mask, const void* y, const float* relu_scale,
-                                const float* relu_shift, const float* coef, int C, long total, void* dy, void* dz,
-                                void* stream) {
-    SCD_F16_FWD(scd_bn_bwd_apply, dout, mask, y, relu_scale, relu_shift, coef, C, total, dy, dz, stream);
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == SCD_DT_BF16) {
-        if (C % 8 || !ew_rows_ok(C / 8)) return SCD_ERR_ARG;
-        long nvec = total / 8;
-        const size_t lds = ew_param_lds(5, C, 8);
-        if (lds > EW_LDS_MAX) return SCD_ERR_ARG;
-        const int g = ew_resident<2>((const void*)bn_bwd_apply_kernel<h16>, lds);
-        hipLaunchKernelGGL((bn_bwd_apply_kernel<h16>), dim3(ew_grid(g, nvec, C / 8)), dim3(256), lds, st,
-                           (const h16*)dout, (const h16*)mask, (const h16*)y, relu_scale, relu_shift, coef, C,
-                           (unsigned)nvec, (h16*)dy, (h16*)dz);
-    } else if (dtype == SCD_DT_F32) {
-        if (C % 4 || !ew_rows_ok(C / 4)) return SCD_ERR_ARG;
-        long nvec = total / 4;
-        const size_t lds = ew_param_lds(5, C, 4);
-        if (lds > EW_LDS_MAX) return SCD_ERR_ARG;
-        const int g = ew_resident<3>((const void*)bn_bwd_apply_kernel<float>, lds);
-        hipLaunchKernelGGL((bn_bwd_apply_kernel<float>), dim3(ew_grid(g, nvec, C / 4)), dim3(256), lds, st, (const float*)dout,
-                           (const float*)mask, (const float*)y, relu_scale, relu_shift, coef, C, (unsigned)nvec, (float*)dy,
-                           (float*)dz);
-    } else {
-        return SCD_ERR_ARG;
-    }
-    SCD_RETURN_LAUNCH();
-}
+#endif  // !SCD_F16_BUILD

@@ -2785,95 +2785,6 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_l1_kernel(WgradParams p) {
     }
 }
 
-// row slices of one reduce launch (the three heads of a fused head weight gradient go to three parameters)
-struct WredSlices {
-    int n;
-    int r0[4], r1[4];
-    long ldn[4], ldc[4], ldt[4];
-    float* dst[4];
-};
-
-// Split reduction: block (row, channel chunk) sums the nsplit slabs of its WRED_CB input channels x T taps of one
-// slab row (coalesced 16-B reads, 8 slab loads in flight per thread, fixed summation order) into LDS, then writes the
-// chunk in the destination's order (OIHW: taps fastest) so consecutive lanes store consecutive words.  The earlier
-// form (one thread per 4 slab columns, stores 4 * ldc apart) read the slabs at ~2.2 TB/s behind its scattered
-// stores (tools/wgrad_bench.py: 30 us for the layer4 conv2 gradient, 7 splits).
-constexpr int WRED_CB = 128;                       // widest channel chunk (narrower when there are few rows)
-
-// slab sum over splits g, g + S, g + 2S, ... of one 4-column unit (8 loads in flight), fixed order
-__device__ __forceinline__ f32x4 wred_sum_strided(const float* src, int n, long zs, int g, int S) {
-    f32x4 a[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) a[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    int z = g;
-    for (; z + 7 * S < n; z += 8 * S) {
-        f32x4 v[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = *(const f32x4*)(src + (long)(z + j * S) * zs);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) a[j] += v[j];
-    }
-#pragma unroll
-    for (int j = 0; j < 7; ++j)
-        if (z + j * S < n) a[j] += *(const f32x4*)(src + (long)(z + j * S) * zs);
-    return ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
-}
-
-// block (row, channel chunk of cb): S thread groups per 4-column unit each sum every S-th split (S > 1 when the
-// chunk has few units and there are many splits: the 64-row layer1 gradient over 256 splits), the S partials are
-// added in LDS in a fixed order, and the chunk is written in the destination's order
-__global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* ws, int nsplit, long zs, int T, int Ci,
-                                                           int cvalid, WredSlices sl, int ncb, int cb, int S,
-                                                           int accumulate, float alpha) {
-    extern __shared__ float red[];                 // [T][cb + 1], then the S-way partials [S][units] (f32x4)
-    const int tid = threadIdx.x;
-    const int cbk = blockIdx.x % ncb;
-    int rr = blockIdx.x / ncb;
-    int s = 0;
-    while (s < sl.n - 1 && rr >= sl.r1[s] - sl.r0[s]) { rr -= sl.r1[s] - sl.r0[s]; ++s; }
-    const int row = sl.r0[s] + rr;
-    const int c0 = cbk * cb, cn = min(cb, Ci - c0);
-    const int upt = cn >> 2;                       // 4-column units per tap
-    const int units = T * upt;
-    const long KK = (long)T * Ci;
-    const float* src = ws + (long)row * KK + c0;
-    f32x4* part = (f32x4*)(red + ((T * (cb + 1) + 3) & ~3));
-    if (S > 1) {
-        for (int i = tid; i < units * S; i += blockDim.x) {
-            const int u = i % units, g = i / units;
-            const int t = u / upt, j = u - t * upt;
-            part[g * units + u] = wred_sum_strided(src + (long)t * Ci + 4 * j, nsplit, zs, g, S);
-        }
-        __syncthreads();
-    }
-    for (int u = tid; u < units; u += blockDim.x) {
-        const int t = u / upt, j = u - t * upt;
-        f32x4 v;
-        if (S > 1) {
-            v = part[u];
-            for (int g = 1; g < S; ++g) v += part[g * units + u];
-        } else {
-            v = wred_sum_strided(src + (long)t * Ci + 4 * j, nsplit, zs, 0, 1);
-        }
-        v *= alpha;
-        float* d = red + t * (cb + 1) + 4 * j;
-        d[0] = v[0]; d[1] = v[1]; d[2] = v[2]; d[3] = v[3];
-    }
-    __syncthreads();
-    float* drow = sl.dst[s] + rr * sl.ldn[s];
-    const long ldc = sl.ldc[s], ldt = sl.ldt[s];
-    const bool taps_fast = ldt <= ldc;
-    for (int i = tid; i < T * cn; i += blockDim.x) {
-        int c, t;
-        if (taps_fast) { c = i / T; t = i - c * T; }
-        else { t = i / cn; c = i - t * cn; }
-        if (c0 + c >= cvalid) continue;
-        const float v = red[t * (cb + 1) + c];
-        float* d = drow + (c0 + c) * ldc + t * ldt;
-        *d = accumulate ? (*d + v) : v;
-    }
-}
-
 template <typename T, int BM, int BN>
 int launch_gemm(GemmParams& p, int Mtot_tiles, hipStream_t st, int ks = 1) {
     if (p.res) {
@@ -3555,20 +3466,18 @@ static int launch_tiled(int dtype, GemmParams& p, int nphase, const scd_gemm_pha
     const int tiles = fill_tiles(p, nphase, phases, narrow ? 256 : 128, cdiv(p.Co, narrow ? 64 : 128));
     if (tiles == 0) return 0;
     if (!fill_ranges(dtype, p, false)) return SCD_ERR_ARG;
-    if (dtype == SCD_DT_BF16) {
-        if (narrow) return launch_gemm<h16, 256, 64>(p, tiles, st);
-        // intra-workgroup split K: grids of at most 1.5 tiles per CU with >= 16 K stages
+    return scd_dispatch_dtype(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        if (narrow) return launch_gemm<T, 256, 64>(p, tiles, st);
+        // intra-workgroup split K (16-bit types): grids of at most 1.5 tiles per CU with >= 16 K stages
         int ks = 1;
-        if (!p.head_on) {
+        if (sizeof(T) == 2 && !p.head_on) {
             int kt = 0;
             for (int i = 0; i < nphase; ++i) kt = std::max(kt, phases[i].ntaps * (p.Ci / 64));
             if (kt >= 16 && 2 * (long)tiles <= 3L * num_cus()) ks = 2;
         }
-        return launch_gemm<h16, 128, 128>(p, tiles, st, ks);
-    }
-    if (dtype == SCD_DT_F32)
-        return narrow ? launch_gemm<float, 256, 64>(p, tiles, st) : launch_gemm<float, 128, 128>(p, tiles, st);
-    return SCD_ERR_ARG;
+        return launch_gemm<T, 128, 128>(p, tiles, st, ks);
+    });
 }
 
 static int conv_gemm_launch(int dtype, GemmParams& p, int nphase, const scd_gemm_phase* phases, void* stream) {
@@ -3709,10 +3618,6 @@ extern "C" int scd_conv_gemm_heads_keep(int dtype, const void* x, const void* w,
     ph.Qh = H; ph.Qw = W; ph.rho_h = 0; ph.rho_w = 0; ph.ntaps = 9;
     for (int t = 0; t < 9; ++t) { ph.dh[t] = t / 3 - 1; ph.dw[t] = t % 3 - 1; ph.wt[t] = t; }
     return conv_gemm_launch(dtype, p, 1, &ph, stream);
-}
-
-extern "C" size_t scd_conv_wgrad_workspace(int Cg, int T, int Ci, int nsplit) {
-    return (size_t)nsplit * Cg * T * Ci * sizeof(float);
 }
 
 static void wgrad_tile(int dtype, long M, int Cg, int& tm, int& tn) {
@@ -3896,14 +3801,115 @@ extern "C" int scd_conv_wgrad(int dtype, const void* g, const void* x, float* ws
     p.nsplit = nsplit;
     dim3 grid(p.ntm * p.ntn * nsplit);
     hipStream_t st = (hipStream_t)stream;
-    if (dtype != SCD_DT_BF16 && dtype != SCD_DT_F32) return SCD_ERR_ARG;
-    // fast addressing when a stage of KP pixels stays inside one image and one row block
-    const int KP = dtype == SCD_DT_BF16 ? 64 : 32;
-    const bool fastok = ((long)Ho * Wo) % KP == 0 && chunk % KP == 0;
-    const int fx = !fastok ? 0 : (Wo % KP == 0 ? 1 : (KP % Wo == 0 ? 2 : 0));
-    if (dtype == SCD_DT_BF16) launch_wgrad_tiled<h16>(BM, fx, grid, st, p);
-    else launch_wgrad_tiled<float>(BM, fx, grid, st, p);
-    SCD_RETURN_LAUNCH();
+    return scd_dispatch_dtype(dtype, [&](auto tag) {
+        using E = typename decltype(tag)::type;        // (T is the tap count here)
+        // fast addressing when a stage of KP pixels stays inside one image and one row block
+        constexpr int KP = 128 / sizeof(E);
+        const bool fastok = ((long)Ho * Wo) % KP == 0 && chunk % KP == 0;
+        const int fx = !fastok ? 0 : (Wo % KP == 0 ? 1 : (KP % Wo == 0 ? 2 : 0));
+        launch_wgrad_tiled<E>(BM, fx, grid, st, p);
+        SCD_RETURN_LAUNCH();
+    });
+}
+
+// ---------------------------------------------------------------- weight-gradient workspace and split reduction
+// fp32 slabs in, fp32 gradients out, no dtype: the first build alone holds these entry points and their kernel.
+#ifndef SCD_F16_BUILD
+namespace {
+
+// row slices of one reduce launch (the three heads of a fused head weight gradient go to three parameters)
+struct WredSlices {
+    int n;
+    int r0[4], r1[4];
+    long ldn[4], ldc[4], ldt[4];
+    float* dst[4];
+};
+
+// Split reduction: block (row, channel chunk) sums the nsplit slabs of its WRED_CB input channels x T taps of one
+// slab row (coalesced 16-B reads, 8 slab loads in flight per thread, fixed summation order) into LDS, then writes the
+// chunk in the destination's order (OIHW: taps fastest) so consecutive lanes store consecutive words.  The earlier
+// form (one thread per 4 slab columns, stores 4 * ldc apart) read the slabs at ~2.2 TB/s behind its scattered
+// stores (tools/wgrad_bench.py: 30 us for the layer4 conv2 gradient, 7 splits).
+constexpr int WRED_CB = 128;                       // widest channel chunk (narrower when there are few rows)
+
+// slab sum over splits g, g + S, g + 2S, ... of one 4-column unit (8 loads in flight), fixed order
+__device__ __forceinline__ f32x4 wred_sum_strided(const float* src, int n, long zs, int g, int S) {
+    f32x4 a[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) a[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    int z = g;
+    for (; z + 7 * S < n; z += 8 * S) {
+        f32x4 v[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = *(const f32x4*)(src + (long)(z + j * S) * zs);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) a[j] += v[j];
+    }
+#pragma unroll
+    for (int j = 0; j < 7; ++j)
+        if (z + j * S < n) a[j] += *(const f32x4*)(src + (long)(z + j * S) * zs);
+    return ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
+}
+
+// block (row, channel chunk of cb): S thread groups per 4-column unit each sum every S-th split (S > 1 when the
+// chunk has few units and there are many splits: the 64-row layer1 gradient over 256 splits), the S partials are
+// added in LDS in a fixed order, and the chunk is written in the destination's order
+__global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* ws, int nsplit, long zs, int T, int Ci,
+                                                           int cvalid, WredSlices sl, int ncb, int cb, int S,
+                                                           int accumulate, float alpha) {
+    extern __shared__ float red[];                 // [T][cb + 1], then the S-way partials [S][units] (f32x4)
+    const int tid = threadIdx.x;
+    const int cbk = blockIdx.x % ncb;
+    int rr = blockIdx.x / ncb;
+    int s = 0;
+    while (s < sl.n - 1 && rr >= sl.r1[s] - sl.r0[s]) { rr -= sl.r1[s] - sl.r0[s]; ++s; }
+    const int row = sl.r0[s] + rr;
+    const int c0 = cbk * cb, cn = min(cb, Ci - c0);
+    const int upt = cn >> 2;                       // 4-column units per tap
+    const int units = T * upt;
+    const long KK = (long)T * Ci;
+    const float* src = ws + (long)row * KK + c0;
+    f32x4* part = (f32x4*)(red + ((T * (cb + 1) + 3) & ~3));
+    if (S > 1) {
+        for (int i = tid; i < units * S; i += blockDim.x) {
+            const int u = i % units, g = i / units;
+            const int t = u / upt, j = u - t * upt;
+            part[g * units + u] = wred_sum_strided(src + (long)t * Ci + 4 * j, nsplit, zs, g, S);
+        }
+        __syncthreads();
+    }
+    for (int u = tid; u < units; u += blockDim.x) {
+        const int t = u / upt, j = u - t * upt;
+        f32x4 v;
+        if (S > 1) {
+            v = part[u];
+            for (int g = 1; g < S; ++g) v += part[g * units + u];
+        } else {
+            v = wred_sum_strided(src + (long)t * Ci + 4 * j, nsplit, zs, 0, 1);
+        }
+        v *= alpha;
+        float* d = red + t * (cb + 1) + 4 * j;
+        d[0] = v[0]; d[1] = v[1]; d[2] = v[2]; d[3] = v[3];
+    }
+    __syncthreads();
+    float* drow = sl.dst[s] + rr * sl.ldn[s];
+    const long ldc = sl.ldc[s], ldt = sl.ldt[s];
+    const bool taps_fast = ldt <= ldc;
+    for (int i = tid; i < T * cn; i += blockDim.x) {
+        int c, t;
+        if (taps_fast) { c = i / T; t = i - c * T; }
+        else { t = i / cn; c = i - t * cn; }
+        if (c0 + c >= cvalid) continue;
+        const float v = red[t * (cb + 1) + c];
+        float* d = drow + (c0 + c) * ldc + t * ldt;
+        *d = accumulate ? (*d + v) : v;
+    }
+}
+
+}  // namespace
+
+extern "C" size_t scd_conv_wgrad_workspace(int Cg, int T, int Ci, int nsplit) {
+    return (size_t)nsplit * Cg * T * Ci * sizeof(float);
 }
 
 extern "C" int scd_wgrad_reduce_rows(const float* ws, int nsplit, int Cg, int T, int Ci, int nslices, const int* r0,
@@ -3942,3 +3948,4 @@ extern "C" int scd_wgrad_reduce(const float* ws, int nsplit, int Cg, int T, int 
     return scd_wgrad_reduce_rows(ws, nsplit, Cg, T, Ci, 1, &r0, &r1, &ld_n, &ld_c, &ld_t, &dst, cvalid, accumulate,
                                  alpha, stream);
 }
+#endif  // !SCD_F16_BUILD

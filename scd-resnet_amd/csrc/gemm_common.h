@@ -1,6 +1,4 @@
-// Shared by the implicit-GEMM convolution sources.  For now that is conv_gemm.hip alone and this header holds only
-// the library's environment switches; GemmParams, the device helpers and the launcher declarations join it when the
-// kernel families get a translation unit each.
+// The environment switches of conv_gemm.hip, which holds every implicit-GEMM kernel family and its launcher.
 #pragma once
 #include <stdlib.h>
 

@@ -176,14 +176,6 @@ __global__ __launch_bounds__(256) void pack_weights_batched_kernel(const scd_pac
     }
 }
 
-extern "C" int scd_pack_weights_batched(int dtype, const scd_pack_desc* descs, int n, long total, void* stream) {
-    SCD_F16_FWD(scd_pack_weights_batched, descs, n, total, stream);
-    if (n < 1 || total < 1 || total >= (1L << 31) || total % PACK_UNIT || (dtype != SCD_DT_BF16 && dtype != SCD_DT_F32)) return SCD_ERR_ARG;
-    hipLaunchKernelGGL(pack_weights_batched_kernel, dim3((unsigned)(total / PACK_UNIT)), dim3(256), 0, (hipStream_t)stream,
-                       descs, n, dtype == SCD_DT_BF16 ? 1 : 0);
-    SCD_RETURN_LAUNCH();
-}
-
 // ---------------------------------------------------------------- stem im2col
 template <typename T>
 __global__ void im2col_stem_kernel(const float* x, T* cols, int N, int H, int W, int Ho, int Wo, int kh, int kw,
@@ -689,41 +681,6 @@ __global__ __launch_bounds__(512) void heads_bwd_kernel(const T* hid, int N, int
     }
 }
 
-struct HeadsGrad {
-    float* dw1[4];
-    float* db1[4];
-    float* db0[4];
-};
-
-__global__ void heads_bwd_weight_finalize_kernel(double* acc, int accsz, HeadsDesc d, HeadsGrad g, int accumulate,
-                                                 double alpha) {
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < accsz; i += gridDim.x * blockDim.x) {
-        double s = 0.0;
-        for (int r = 0; r < SCD_STAT_REPLICAS; ++r) {
-            s += acc[(long)r * accsz + i];
-            acc[(long)r * accsz + i] = 0.0;
-        }
-        float* dst;
-        if (i < d.nout * d.Hd) {
-            const int row = i / d.Hd, cl = i - (i / d.Hd) * d.Hd;
-            int h = 0;
-            while (h + 1 < d.nh && row >= d.orow[h + 1]) ++h;
-            dst = g.dw1[h] + (row - d.orow[h]) * d.Hd + cl;
-        } else if (i < d.nout * d.Hd + d.nout) {
-            const int row = i - d.nout * d.Hd;
-            int h = 0;
-            while (h + 1 < d.nh && row >= d.orow[h + 1]) ++h;
-            dst = g.db1[h] + (row - d.orow[h]);
-        } else {
-            const int c = i - d.nout * d.Hd - d.nout;
-            const int h = c / d.Hd;
-            dst = g.db0[h] + (c - h * d.Hd);
-        }
-        s *= alpha;
-        *dst = accumulate ? (*dst + (float)s) : (float)s;
-    }
-}
-
 bool make_desc(HeadsDesc& d, int nh, int Hd, const int* od) {
     if (nh < 1 || nh > 4 || Hd % 8 != 0) return false;
     d.nh = nh; d.Hd = Hd; d.nout = 0;
@@ -739,197 +696,99 @@ bool make_desc(HeadsDesc& d, int nh, int Hd, const int* od) {
     return d.nout * Hd <= 8 * 512;
 }
 
-// ---------------------------------------------------------------- Adam (torch.optim.Adam, foreach form)
-__global__ void adam_kernel(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2,
-                            float eps, float bc1, float bc2_sqrt, float gscale) {
-    const float step = lr / bc1;
-    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-        const float gi = g[i] * gscale;
-        float mi = m[i];
-        mi = mi + (1.f - b1) * (gi - mi);                 // exp_avg.lerp_(grad, 1-beta1)
-        float vi = v[i] * b2 + (1.f - b2) * gi * gi;      // exp_avg_sq.mul_(b2).addcmul_(g,g,1-b2)
-        const float denom = sqrtf(vi) / bc2_sqrt + eps;
-        p[i] = p[i] - step * (mi / denom);
-        m[i] = mi;
-        v[i] = vi;
-    }
-}
-
-// Device-resident step state (hyper = {lr, step}, fp64) so a captured step graph replays with the current learning
-// rate and bias corrections: the tick advances the step, the update kernel derives the corrections exactly as
-// the host path does (fp64 powers rounded to fp32, torch/optim/adam.py _single_tensor_adam).
-// skip (optional): a device word (the peer-memory SyncBN error word, scdhip/peer.py); non-zero = this step's gradients
-// were formed from unreduced (NaN-poisoned) statistics: neither the step count nor any parameter or moment changes.
-__global__ void adam_tick_kernel(double* hyper, const unsigned long long* skip) {
-    if (skip && *skip) return;
-    if (threadIdx.x == 0) hyper[1] = hyper[1] + 1.0;
-}
-
-__global__ void adam_dev_kernel(float* p, const float* g, float* m, float* v, long n, const double* hyper, float b1,
-                                float b2, float eps, float gscale, const unsigned long long* skip) {
-    if (skip && *skip) return;
-    const double s = hyper[1];
-    const float lr = (float)hyper[0];
-    const float bc1 = (float)(1.0 - pow((double)b1, s));
-    const float bc2 = (float)(1.0 - pow((double)b2, s));
-    const float step = lr / bc1;
-    const float bc2_sqrt = sqrtf(bc2);
-    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-        const float gi = g[i] * gscale;
-        float mi = m[i];
-        mi = mi + (1.f - b1) * (gi - mi);
-        float vi = v[i] * b2 + (1.f - b2) * gi * gi;
-        const float denom = sqrtf(vi) / bc2_sqrt + eps;
-        p[i] = p[i] - step * (mi / denom);
-        m[i] = mi;
-        v[i] = vi;
-    }
-}
-
-// ---------------------------------------------------------------- SGD (torch.optim.SGD, single-tensor form)
-// networkFactory.py:84-89: SGD(lr, momentum 0.9, weight_decay 1e-4).  d = g + wd*p; the momentum buffer starts as a
-// copy of d on the buffer's first step, then buf = mom*buf + (1-dampening)*d; the update uses d + mom*buf (nesterov) or
-// buf.  hyper = {lr, step, initialised, snapshot} fp64 in device memory: the tick advances the step and moves the
-// buffer's "initialised" flag into the snapshot the update reads (set to 1 for the next step), so a buffer re-created
-// mid-training (flag cleared by the host) starts as torch's does, not from the global step count.
-__global__ void sgd_tick_kernel(double* hyper, const unsigned long long* skip) {
-    if (skip && *skip) return;
-    if (threadIdx.x == 0) {
-        hyper[1] = hyper[1] + 1.0;
-        hyper[3] = hyper[2];
-        hyper[2] = 1.0;
-    }
-}
-
-__global__ void sgd_dev_kernel(float* p, const float* g, float* buf, long n, const double* hyper, float mom, float damp,
-                               float wd, int nesterov, float gscale, const unsigned long long* skip) {
-    if (skip && *skip) return;
-    const float lr = (float)hyper[0];
-    const bool first = hyper[3] == 0.0;
-    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-        const float pi = p[i];
-        float d = g[i] * gscale;
-        if (wd != 0.f) d = d + wd * pi;
-        if (mom != 0.f) {
-            const float b = first ? d : buf[i] * mom + (1.f - damp) * d;
-            buf[i] = b;
-            d = nesterov ? d + mom * b : b;
-        }
-        p[i] = pi - lr * d;
-    }
-}
-
 inline int ew_blocks(long n) { return (int)std::min<long>(8192, std::max<long>(1, (n + 255) / 256)); }
 
 SCD_KERNEL_NS_END
 }  // namespace
+
+extern "C" int scd_pack_weights_batched(int dtype, const scd_pack_desc* descs, int n, long total, void* stream) {
+    SCD_F16_FWD(scd_pack_weights_batched, descs, n, total, stream);
+    if (n < 1 || total < 1 || total >= (1L << 31) || total % PACK_UNIT || (dtype != SCD_DT_BF16 && dtype != SCD_DT_F32)) return SCD_ERR_ARG;
+    hipLaunchKernelGGL(pack_weights_batched_kernel, dim3((unsigned)(total / PACK_UNIT)), dim3(256), 0, (hipStream_t)stream,
+                       descs, n, dtype == SCD_DT_BF16 ? 1 : 0);
+    SCD_RETURN_LAUNCH();
+}
 
 extern "C" int scd_pack_weight(int dtype, const float* w, void* out, int A, int B, int T, int mode, int ldp, int row_off,
                                void* stream) {
     SCD_F16_FWD(scd_pack_weight, w, out, A, B, T, mode, ldp, row_off, stream);
     if (mode == 3 && (T != 9 || ldp < 4 * A)) return SCD_ERR_ARG;
     const long total = (long)(mode == 0 ? A : mode == 3 ? 4 * B : B) * ldp;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == SCD_DT_BF16)
-        hipLaunchKernelGGL((pack_weight_kernel<h16>), dim3(ew_blocks(total)), dim3(256), 0, st, w, (h16*)out, A, B,
-                           T, mode, ldp, row_off);
-    else if (dtype == SCD_DT_F32)
-        hipLaunchKernelGGL((pack_weight_kernel<float>), dim3(ew_blocks(total)), dim3(256), 0, st, w, (float*)out, A, B, T,
-                           mode, ldp, row_off);
-    else
-        return SCD_ERR_ARG;
-    SCD_RETURN_LAUNCH();
+    return scd_dispatch_dtype(dtype, [&](auto tag) {
+        using E = typename decltype(tag)::type;        // (T is the tap count here)
+        hipLaunchKernelGGL((pack_weight_kernel<E>), dim3(ew_blocks(total)), dim3(256), 0, (hipStream_t)stream, w,
+                           (E*)out, A, B, T, mode, ldp, row_off);
+        SCD_RETURN_LAUNCH();
+    });
 }
 
 extern "C" int scd_im2col_stem(int dtype, const float* x, void* cols, int N, int H, int W, int Ho, int Wo, int kh,
                                int kw, int stride, int pad, int Kpad, void* stream) {
     SCD_F16_FWD(scd_im2col_stem, x, cols, N, H, W, Ho, Wo, kh, kw, stride, pad, Kpad, stream);
-    hipStream_t st = (hipStream_t)stream;
     if (Kpad % 8 || Kpad < kh * kw) return SCD_ERR_ARG;
-    const long total = (long)N * Ho * Wo * (Kpad / (dtype == SCD_DT_BF16 ? 8 : 4));
-    if (dtype == SCD_DT_BF16)
-        hipLaunchKernelGGL((im2col_stem_kernel<h16>), dim3(ew_blocks(total)), dim3(256), 0, st, x, (h16*)cols, N, H,
-                           W, Ho, Wo, kh, kw, stride, pad, Kpad);
-    else if (dtype == SCD_DT_F32)
-        hipLaunchKernelGGL((im2col_stem_kernel<float>), dim3(ew_blocks(total)), dim3(256), 0, st, x, (float*)cols, N, H,
-                           W, Ho, Wo, kh, kw, stride, pad, Kpad);
-    else
-        return SCD_ERR_ARG;
-    SCD_RETURN_LAUNCH();
+    return scd_dispatch_dtype(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        constexpr int E = 16 / sizeof(T);
+        const long total = (long)N * Ho * Wo * (Kpad / E);
+        hipLaunchKernelGGL((im2col_stem_kernel<T>), dim3(ew_blocks(total)), dim3(256), 0, (hipStream_t)stream, x,
+                           (T*)cols, N, H, W, Ho, Wo, kh, kw, stride, pad, Kpad);
+        SCD_RETURN_LAUNCH();
+    });
 }
 
 extern "C" int scd_stem_pool_fwd(int dtype, const void* y, const float* scale, const float* shift, void* out,
                                  uint8_t* argmax, int N, int H, int W, int C, int Ho, int Wo, void* stream) {
     SCD_F16_FWD(scd_stem_pool_fwd, y, scale, shift, out, argmax, N, H, W, C, Ho, Wo, stream);
-    hipStream_t st = (hipStream_t)stream;
-    const int E = dtype == SCD_DT_BF16 ? 8 : 4;
-    if (C % E) return SCD_ERR_ARG;
-    const long total = (long)N * ((Ho + SPR - 1) / SPR) * Wo * (C / E);
-    if (total >= (1L << 32)) return SCD_ERR_ARG;
-    if (dtype == SCD_DT_BF16)
-        hipLaunchKernelGGL((stem_pool_fwd_kernel<h16>), dim3(ew_blocks(total)), dim3(256), 0, st, (const h16*)y,
-                           scale, shift, (h16*)out, argmax, N, H, W, C, Ho, Wo);
-    else if (dtype == SCD_DT_F32)
-        hipLaunchKernelGGL((stem_pool_fwd_kernel<float>), dim3(ew_blocks(total)), dim3(256), 0, st, (const float*)y,
-                           scale, shift, (float*)out, argmax, N, H, W, C, Ho, Wo);
-    else
-        return SCD_ERR_ARG;
-    SCD_RETURN_LAUNCH();
+    return scd_dispatch_dtype(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        constexpr int E = 16 / sizeof(T);
+        if (C % E) return SCD_ERR_ARG;
+        const long total = (long)N * ((Ho + SPR - 1) / SPR) * Wo * (C / E);
+        if (total >= (1L << 32)) return SCD_ERR_ARG;
+        hipLaunchKernelGGL((stem_pool_fwd_kernel<T>), dim3(ew_blocks(total)), dim3(256), 0, (hipStream_t)stream,
+                           (const T*)y, scale, shift, (T*)out, argmax, N, H, W, C, Ho, Wo);
+        SCD_RETURN_LAUNCH();
+    });
 }
 
 extern "C" int scd_stem_pool_bwd(int dtype, const void* dout, const uint8_t* argmax, const void* y, const float* scale,
                                  const float* shift, void* dz, int N, int H, int W, int C, int Ho, int Wo, void* stream) {
     SCD_F16_FWD(scd_stem_pool_bwd, dout, argmax, y, scale, shift, dz, N, H, W, C, Ho, Wo, stream);
-    hipStream_t st = (hipStream_t)stream;
-    const int E = dtype == SCD_DT_BF16 ? 8 : 4;
-    if (C % E) return SCD_ERR_ARG;
-    const long total = (long)N * H * W * (C / E);
-    if (dtype == SCD_DT_BF16)
-        hipLaunchKernelGGL((stem_pool_bwd_kernel<h16>), dim3(ew_blocks(total)), dim3(256), 0, st,
-                           (const h16*)dout, argmax, (const h16*)y, scale, shift, (h16*)dz, N, H, W, C, Ho, Wo);
-    else if (dtype == SCD_DT_F32)
-        hipLaunchKernelGGL((stem_pool_bwd_kernel<float>), dim3(ew_blocks(total)), dim3(256), 0, st, (const float*)dout,
-                           argmax, (const float*)y, scale, shift, (float*)dz, N, H, W, C, Ho, Wo);
-    else
-        return SCD_ERR_ARG;
-    SCD_RETURN_LAUNCH();
+    return scd_dispatch_dtype(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        constexpr int E = 16 / sizeof(T);
+        if (C % E) return SCD_ERR_ARG;
+        const long total = (long)N * H * W * (C / E);
+        hipLaunchKernelGGL((stem_pool_bwd_kernel<T>), dim3(ew_blocks(total)), dim3(256), 0, (hipStream_t)stream,
+                           (const T*)dout, argmax, (const T*)y, scale, shift, (T*)dz, N, H, W, C, Ho, Wo);
+        SCD_RETURN_LAUNCH();
+    });
 }
 
 extern "C" int scd_stem_pool_bwd_bn(int dtype, const void* dout, const uint8_t* argmax, const void* y, const float* scale,
                                     const float* shift, const float* mean, const float* invstd, void* dz, double* stats,
                                     int N, int H, int W, int C, int Ho, int Wo, void* stream) {
     SCD_F16_FWD(scd_stem_pool_bwd_bn, dout, argmax, y, scale, shift, mean, invstd, dz, stats, N, H, W, C, Ho, Wo, stream);
-    hipStream_t st = (hipStream_t)stream;
-    const int E = dtype == SCD_DT_BF16 ? 8 : 4;
-    if (C % E || 256 % (C / E)) return SCD_ERR_ARG;
-    const long total = (long)N * H * W * (C / E);
-    if (H == 2 * Ho && W == 2 * Wo && (long)N * H * W * C < (1L << 31)) {
-        static const int g2b = resident_grid((const void*)stem_pool_bwd_bn_2x2_kernel<h16>, 256);
-        static const int g2f = resident_grid((const void*)stem_pool_bwd_bn_2x2_kernel<float>, 256);
-        const long blocks2 = (long)N * Ho * Wo * (C / E);
-        const int grid = (int)std::min<long>(dtype == SCD_DT_BF16 ? g2b : g2f, (blocks2 + 255) / 256);
-        if (dtype == SCD_DT_BF16)
-            hipLaunchKernelGGL((stem_pool_bwd_bn_2x2_kernel<h16>), dim3(grid), dim3(256), 0, st, (const h16*)dout,
-                               argmax, (const h16*)y, scale, shift, mean, invstd, (h16*)dz, stats, N, C, Ho, Wo);
-        else if (dtype == SCD_DT_F32)
-            hipLaunchKernelGGL((stem_pool_bwd_bn_2x2_kernel<float>), dim3(grid), dim3(256), 0, st, (const float*)dout,
-                               argmax, (const float*)y, scale, shift, mean, invstd, (float*)dz, stats, N, C, Ho, Wo);
-        else
-            return SCD_ERR_ARG;
+    return scd_dispatch_dtype(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        constexpr int E = 16 / sizeof(T);
+        hipStream_t st = (hipStream_t)stream;
+        if (C % E || 256 % (C / E)) return SCD_ERR_ARG;
+        const long total = (long)N * H * W * (C / E);
+        if (H == 2 * Ho && W == 2 * Wo && (long)N * H * W * C < (1L << 31)) {
+            static const int g2 = resident_grid((const void*)stem_pool_bwd_bn_2x2_kernel<T>, 256);
+            const long blocks2 = (long)N * Ho * Wo * (C / E);
+            const int grid = (int)std::min<long>(g2, (blocks2 + 255) / 256);
+            hipLaunchKernelGGL((stem_pool_bwd_bn_2x2_kernel<T>), dim3(grid), dim3(256), 0, st, (const T*)dout, argmax,
+                               (const T*)y, scale, shift, mean, invstd, (T*)dz, stats, N, C, Ho, Wo);
+            SCD_RETURN_LAUNCH();
+        }
+        static const int g = resident_grid((const void*)stem_pool_bwd_bn_kernel<T>, 256);
+        const int blocks = (int)std::min<long>(g, (total + 255) / 256);
+        hipLaunchKernelGGL((stem_pool_bwd_bn_kernel<T>), dim3(blocks), dim3(256), 0, st, (const T*)dout, argmax,
+                           (const T*)y, scale, shift, mean, invstd, (T*)dz, stats, N, H, W, C, Ho, Wo);
         SCD_RETURN_LAUNCH();
-    }
-    static const int gb = resident_grid((const void*)stem_pool_bwd_bn_kernel<h16>, 256);
-    static const int gf = resident_grid((const void*)stem_pool_bwd_bn_kernel<float>, 256);
-    const int blocks = (int)std::min<long>(dtype == SCD_DT_BF16 ? gb : gf, (total + 255) / 256);
-    if (dtype == SCD_DT_BF16)
-        hipLaunchKernelGGL((stem_pool_bwd_bn_kernel<h16>), dim3(blocks), dim3(256), 0, st, (const h16*)dout, argmax,
-                           (const h16*)y, scale, shift, mean, invstd, (h16*)dz, stats, N, H, W, C, Ho, Wo);
-    else if (dtype == SCD_DT_F32)
-        hipLaunchKernelGGL((stem_pool_bwd_bn_kernel<float>), dim3(blocks), dim3(256), 0, st, (const float*)dout, argmax,
-                           (const float*)y, scale, shift, mean, invstd, (float*)dz, stats, N, H, W, C, Ho, Wo);
-    else
-        return SCD_ERR_ARG;
-    SCD_RETURN_LAUNCH();
+    });
 }
 
 extern "C" int scd_heads_fwd(int dtype, const void* hid, int N, int HW, int nh, int Hd, const int* od,
@@ -937,26 +796,18 @@ extern "C" int scd_heads_fwd(int dtype, const void* hid, int N, int HW, int nh, 
     SCD_F16_FWD(scd_heads_fwd, hid, N, HW, nh, Hd, od, w1, b1, outs, stream);
     HeadsDesc d;
     if (!make_desc(d, nh, Hd, od)) return SCD_ERR_ARG;
-    const int E = dtype == SCD_DT_BF16 ? 8 : 4;
-    const int cph = Hd / E;
-    if (cph > 64 || (cph & (cph - 1))) return SCD_ERR_ARG;
-    for (int h = 0; h < nh; ++h) { d.w1[h] = w1[h]; d.b1[h] = b1[h]; d.out[h] = outs[h]; }
-    hipStream_t st = (hipStream_t)stream;
-    const long total = (long)N * HW * nh * cph;
-    const int blocks = (int)std::min<long>(16384, (total + 255) / 256);
-    if (dtype == SCD_DT_BF16)
-        hipLaunchKernelGGL((heads_fwd_kernel<h16>), dim3(blocks), dim3(256), 0, st, (const h16*)hid, N, HW, d);
-    else if (dtype == SCD_DT_F32)
-        hipLaunchKernelGGL((heads_fwd_kernel<float>), dim3(blocks), dim3(256), 0, st, (const float*)hid, N, HW, d);
-    else
-        return SCD_ERR_ARG;
-    SCD_RETURN_LAUNCH();
-}
-
-extern "C" size_t scd_heads_bwd_accsize(int nh, int Hd, const int* od) {
-    int nout = 0;
-    for (int h = 0; h < nh; ++h) nout += od[h];
-    return (size_t)SCD_STAT_REPLICAS * (nout * Hd + nout + nh * Hd) * sizeof(double);
+    return scd_dispatch_dtype(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        constexpr int E = 16 / sizeof(T);
+        const int cph = Hd / E;
+        if (cph > 64 || (cph & (cph - 1))) return SCD_ERR_ARG;
+        for (int h = 0; h < nh; ++h) { d.w1[h] = w1[h]; d.b1[h] = b1[h]; d.out[h] = outs[h]; }
+        const long total = (long)N * HW * nh * cph;
+        const int blocks = (int)std::min<long>(16384, (total + 255) / 256);
+        hipLaunchKernelGGL((heads_fwd_kernel<T>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const T*)hid, N,
+                           HW, d);
+        SCD_RETURN_LAUNCH();
+    });
 }
 
 extern "C" int scd_heads_bwd(int dtype, const void* hid, int N, int HW, int nh, int Hd, const int* od,
@@ -965,74 +816,29 @@ extern "C" int scd_heads_bwd(int dtype, const void* hid, int N, int HW, int nh, 
     SCD_F16_FWD(scd_heads_bwd, hid, N, HW, nh, Hd, od, w1, douts, dhid, acc, stream);
     HeadsDesc d;
     if (!make_desc(d, nh, Hd, od)) return SCD_ERR_ARG;
-    const int E = dtype == SCD_DT_BF16 ? 8 : 4;
-    const int cpp = nh * Hd / E;
-    if (cpp > 256 || (Hd % E)) return SCD_ERR_ARG;
-    for (int h = 0; h < nh; ++h) { d.w1[h] = w1[h]; d.dout[h] = douts[h]; }
-    const int accsz = d.nout * Hd + d.nout + nh * Hd;
-    const long P = (long)N * HW;
-    if (P * nh * Hd >= (1L << 31)) return SCD_ERR_ARG;     // 32-bit element offsets
-    const int G = 512 / cpp;                                // pixel lanes (cpp <= 256 -> G >= 2)
-    const int threads = G * cpp;
-    const int PXB = 2048;                              // one 1-per-CU round at B=32, 128x128
-    const int blocks = cdiv(P, PXB);
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == SCD_DT_BF16)
-        hipLaunchKernelGGL((heads_bwd_kernel<h16, 8>), dim3(blocks), dim3(threads), 0, st, (const h16*)hid, N,
-                           HW, d, (h16*)dhid, acc, accsz, PXB);
-    else if (dtype == SCD_DT_F32)
-        hipLaunchKernelGGL((heads_bwd_kernel<float, 4>), dim3(blocks), dim3(threads), 0, st, (const float*)hid, N, HW,
-                           d, (float*)dhid, acc, accsz, PXB);
-    else
-        return SCD_ERR_ARG;
-    SCD_RETURN_LAUNCH();
-}
-
-extern "C" int scd_heads_bwd_weight_finalize(double* acc, int nh, int Hd, const int* od, float* const* dw1,
-                                             float* const* db1, float* const* db0, int accumulate, float alpha, void* stream) {
-    HeadsDesc d;
-    if (!make_desc(d, nh, Hd, od)) return SCD_ERR_ARG;
-    HeadsGrad g;
-    for (int h = 0; h < 4; ++h) {
-        g.dw1[h] = h < nh ? dw1[h] : nullptr;
-        g.db1[h] = h < nh ? db1[h] : nullptr;
-        g.db0[h] = h < nh ? db0[h] : nullptr;
-    }
-    const int accsz = d.nout * Hd + d.nout + nh * Hd;
-    hipLaunchKernelGGL(heads_bwd_weight_finalize_kernel, dim3(cdiv(accsz, 256)), dim3(256), 0, (hipStream_t)stream, acc,
-                       accsz, d, g, accumulate, (double)alpha);
-    SCD_RETURN_LAUNCH();
-}
-
-extern "C" int scd_adam_step(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2,
-                             float eps, float bc1, float bc2, float gscale, void* stream) {
-    hipLaunchKernelGGL(adam_kernel, dim3(ew_blocks(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, beta1,
-                       beta2, eps, bc1, sqrtf(bc2), gscale);
-    SCD_RETURN_LAUNCH();
-}
-
-extern "C" int scd_adam_step_dev(float* p, const float* g, float* m, float* v, long n, double* hyper, float beta1,
-                                 float beta2, float eps, float gscale, const unsigned long long* skip, void* stream) {
-    if (!hyper) return SCD_ERR_ARG;
-    hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, hyper, skip);
-    hipLaunchKernelGGL(adam_dev_kernel, dim3(ew_blocks(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n,
-                       (const double*)hyper, beta1, beta2, eps, gscale, skip);
-    SCD_RETURN_LAUNCH();
-}
-
-extern "C" int scd_sgd_step_dev(float* p, const float* g, float* buf, long n, double* hyper, float momentum,
-                                float dampening, float weight_decay, int nesterov, float gscale,
-                                const unsigned long long* skip, void* stream) {
-    if (!hyper || (momentum != 0.f && !buf)) return SCD_ERR_ARG;
-    hipLaunchKernelGGL(sgd_tick_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, hyper, skip);
-    hipLaunchKernelGGL(sgd_dev_kernel, dim3(ew_blocks(n)), dim3(256), 0, (hipStream_t)stream, p, g, buf, n,
-                       (const double*)hyper, momentum, dampening, weight_decay, nesterov, gscale, skip);
-    SCD_RETURN_LAUNCH();
+    return scd_dispatch_dtype(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        constexpr int E = 16 / sizeof(T);
+        const int cpp = nh * Hd / E;
+        if (cpp > 256 || (Hd % E)) return SCD_ERR_ARG;
+        for (int h = 0; h < nh; ++h) { d.w1[h] = w1[h]; d.dout[h] = douts[h]; }
+        const int accsz = d.nout * Hd + d.nout + nh * Hd;
+        const long P = (long)N * HW;
+        if (P * nh * Hd >= (1L << 31)) return SCD_ERR_ARG;     // 32-bit element offsets
+        const int G = 512 / cpp;                                // pixel lanes (cpp <= 256 -> G >= 2)
+        const int threads = G * cpp;
+        const int PXB = 2048;                              // one 1-per-CU round at B=32, 128x128
+        const int blocks = cdiv(P, PXB);
+        hipLaunchKernelGGL((heads_bwd_kernel<T, E>), dim3(blocks), dim3(threads), 0, (hipStream_t)stream,
+                           (const T*)hid, N, HW, d, (T*)dhid, acc, accsz, PXB);
+        SCD_RETURN_LAUNCH();
+    });
 }
 
 extern "C" int scd_heads_bwd_packed(int dtype, const void* hid, int N, int HW, int nh, int Hd, const int* od,
                                     const float* const* w1, const float* const* douts, float dscale, float* packed,
                                     void* dhid, double* acc, void* stream) {
+    SCD_F16_FWD(scd_heads_bwd_packed, hid, N, HW, nh, Hd, od, w1, douts, dscale, packed, dhid, acc, stream);
     return scd_heads_bwd_packed_split(dtype, hid, N, HW, nh, Hd, od, nh, w1, douts, dscale, packed, dhid, acc, stream);
 }
 
@@ -1044,31 +850,28 @@ extern "C" int scd_heads_bwd_packed_split(int dtype, const void* hid, int N, int
     if (!make_desc(d, nh, Hd, od) || !packed || nd < 1 || nd > nh) return SCD_ERR_ARG;
     d.nd = nd;
     d.dstride = nd * Hd;
-    const int E = dtype == SCD_DT_BF16 ? 8 : 4;
-    const int cpp = nd * Hd / E;
-    if (cpp > 256 || (Hd % E)) return SCD_ERR_ARG;
-    for (int h = 0; h < nh; ++h) { d.w1[h] = w1[h]; d.dout[h] = douts[h]; }
-    const int accsz = d.nout * Hd + d.nout + nh * Hd;
-    const long P = (long)N * HW;
-    if (P * nh * Hd >= (1L << 31)) return SCD_ERR_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(heads_pack_kernel, dim3(ew_blocks(P)), dim3(256), 0, st, N, HW, d, dscale, packed);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
-    d.pk = packed;
-    const int G = 512 / cpp;
-    const int threads = G * cpp;
-    const int PXB = 2048;
-    const int blocks = cdiv(P, PXB);
-    if (dtype == SCD_DT_BF16)
-        hipLaunchKernelGGL((heads_bwd_kernel<h16, 8, true>), dim3(blocks), dim3(threads), 0, st, (const h16*)hid,
-                           N, HW, d, (h16*)dhid, acc, accsz, PXB);
-    else if (dtype == SCD_DT_F32)
-        hipLaunchKernelGGL((heads_bwd_kernel<float, 4, true>), dim3(blocks), dim3(threads), 0, st, (const float*)hid,
-                           N, HW, d, (float*)dhid, acc, accsz, PXB);
-    else
-        return SCD_ERR_ARG;
-    SCD_RETURN_LAUNCH();
+    return scd_dispatch_dtype(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        constexpr int E = 16 / sizeof(T);
+        const int cpp = nd * Hd / E;
+        if (cpp > 256 || (Hd % E)) return SCD_ERR_ARG;
+        for (int h = 0; h < nh; ++h) { d.w1[h] = w1[h]; d.dout[h] = douts[h]; }
+        const int accsz = d.nout * Hd + d.nout + nh * Hd;
+        const long P = (long)N * HW;
+        if (P * nh * Hd >= (1L << 31)) return SCD_ERR_ARG;
+        hipStream_t st = (hipStream_t)stream;
+        hipLaunchKernelGGL(heads_pack_kernel, dim3(ew_blocks(P)), dim3(256), 0, st, N, HW, d, dscale, packed);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return (int)e;
+        d.pk = packed;
+        const int G = 512 / cpp;
+        const int threads = G * cpp;
+        const int PXB = 2048;
+        const int blocks = cdiv(P, PXB);
+        hipLaunchKernelGGL((heads_bwd_kernel<T, E, true>), dim3(blocks), dim3(threads), 0, st, (const T*)hid, N, HW,
+                           d, (T*)dhid, acc, accsz, PXB);
+        SCD_RETURN_LAUNCH();
+    });
 }
 
 // ---------------------------------------------------------------- CenterNet heads: sparse-gradient backward
@@ -1262,18 +1065,13 @@ extern "C" int scd_heads_sparse_bwd(int dtype, const void* hid, const void* feat
     for (int h = 0; h < nh; ++h) { d.w1[h] = w1[h]; d.dout[h] = douts[h]; }
     const int accsz = d.nout * Hd + d.nout + nh * Hd;
     const int blocks = cdiv((long)N * K, SP_SPB);
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == SCD_DT_BF16)
-        hipLaunchKernelGGL(heads_sparse_bwd_kernel<h16>, dim3(blocks), dim3(256), 0, st, (const h16*)hid,
-                           (const h16*)feat, N, H, W, Cin, d, dscale, inds, K, (h16*)dhid_s, (h16*)xcol, acc,
-                           accsz, slotmap, ownermap);
-    else if (dtype == SCD_DT_F32)
-        hipLaunchKernelGGL(heads_sparse_bwd_kernel<float>, dim3(blocks), dim3(256), 0, st, (const float*)hid,
-                           (const float*)feat, N, H, W, Cin, d, dscale, inds, K, (float*)dhid_s, (float*)xcol, acc,
-                           accsz, slotmap, ownermap);
-    else
-        return SCD_ERR_ARG;
-    SCD_RETURN_LAUNCH();
+    return scd_dispatch_dtype(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(heads_sparse_bwd_kernel<T>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const T*)hid,
+                           (const T*)feat, N, H, W, Cin, d, dscale, inds, K, (T*)dhid_s, (T*)xcol, acc, accsz, slotmap,
+                           ownermap);
+        SCD_RETURN_LAUNCH();
+    });
 }
 
 extern "C" int scd_heads_sparse_fixup(int dtype, void* dx, const void* cols, int N, int H, int W, int Cin,
@@ -1286,18 +1084,185 @@ extern "C" int scd_heads_sparse_fixup(int dtype, void* dx, const void* cols, int
     if (bn_y && !(mean && invstd && relu_scale && relu_shift && bn_stats)) return SCD_ERR_ARG;
     const int S = N * K;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == SCD_DT_BF16)
-        hipLaunchKernelGGL(heads_sparse_fixup_kernel<h16>, dim3(S), dim3(256), 0, st, (h16*)dx,
-                           (const h16*)cols, N, H, W, Cin, inds, K, slotmap, ownermap, (const h16*)bn_y, mean,
-                           invstd, relu_scale, relu_shift, bn_stats);
-    else if (dtype == SCD_DT_F32)
-        hipLaunchKernelGGL(heads_sparse_fixup_kernel<float>, dim3(S), dim3(256), 0, st, (float*)dx, (const float*)cols,
-                           N, H, W, Cin, inds, K, slotmap, ownermap, (const float*)bn_y, mean, invstd, relu_scale,
-                           relu_shift, bn_stats);
-    else
-        return SCD_ERR_ARG;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(heads_sparse_reset_kernel, dim3(cdiv(S, 256)), dim3(256), 0, st, inds, S, K, H * W, slotmap);
+    return scd_dispatch_dtype(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(heads_sparse_fixup_kernel<T>, dim3(S), dim3(256), 0, st, (T*)dx, (const T*)cols, N, H, W,
+                           Cin, inds, K, slotmap, ownermap, (const T*)bn_y, mean, invstd, relu_scale, relu_shift,
+                           bn_stats);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return (int)e;
+        hipLaunchKernelGGL(heads_sparse_reset_kernel, dim3(cdiv(S, 256)), dim3(256), 0, st, inds, S, K, H * W, slotmap);
+        SCD_RETURN_LAUNCH();
+    });
+}
+
+// ---------------------------------------------------------------- entry points without a dtype
+// The head weight-gradient finalize (fp64 accumulators to fp32 gradients) and the optimizers: the first build alone
+// holds these and their kernels.
+#ifndef SCD_F16_BUILD
+namespace {
+
+struct HeadsGrad {
+    float* dw1[4];
+    float* db1[4];
+    float* db0[4];
+};
+
+__global__ void heads_bwd_weight_finalize_kernel(double* acc, int accsz, HeadsDesc d, HeadsGrad g, int accumulate,
+                                                 double alpha) {
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < accsz; i += gridDim.x * blockDim.x) {
+        double s = 0.0;
+        for (int r = 0; r < SCD_STAT_REPLICAS; ++r) {
+            s += acc[(long)r * accsz + i];
+            acc[(long)r * accsz + i] = 0.0;
+        }
+        float* dst;
+        if (i < d.nout * d.Hd) {
+            const int row = i / d.Hd, cl = i - (i / d.Hd) * d.Hd;
+            int h = 0;
+            while (h + 1 < d.nh && row >= d.orow[h + 1]) ++h;
+            dst = g.dw1[h] + (row - d.orow[h]) * d.Hd + cl;
+        } else if (i < d.nout * d.Hd + d.nout) {
+            const int row = i - d.nout * d.Hd;
+            int h = 0;
+            while (h + 1 < d.nh && row >= d.orow[h + 1]) ++h;
+            dst = g.db1[h] + (row - d.orow[h]);
+        } else {
+            const int c = i - d.nout * d.Hd - d.nout;
+            const int h = c / d.Hd;
+            dst = g.db0[h] + (c - h * d.Hd);
+        }
+        s *= alpha;
+        *dst = accumulate ? (*dst + (float)s) : (float)s;
+    }
+}
+
+// ---------------------------------------------------------------- Adam (torch.optim.Adam, foreach form)
+__global__ void adam_kernel(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2,
+                            float eps, float bc1, float bc2_sqrt, float gscale) {
+    const float step = lr / bc1;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        const float gi = g[i] * gscale;
+        float mi = m[i];
+        mi = mi + (1.f - b1) * (gi - mi);                 // exp_avg.lerp_(grad, 1-beta1)
+        float vi = v[i] * b2 + (1.f - b2) * gi * gi;      // exp_avg_sq.mul_(b2).addcmul_(g,g,1-b2)
+        const float denom = sqrtf(vi) / bc2_sqrt + eps;
+        p[i] = p[i] - step * (mi / denom);
+        m[i] = mi;
+        v[i] = vi;
+    }
+}
+
+// Device-resident step state (hyper = {lr, step}, fp64) so a captured step graph replays with the current learning
+// rate and bias corrections: the tick advances the step, the update kernel derives the corrections exactly as
+// the host path does (fp64 powers rounded to fp32, torch/optim/adam.py _single_tensor_adam).
+// skip (optional): a device word (the peer-memory SyncBN error word, scdhip/peer.py); non-zero = this step's gradients
+// were formed from unreduced (NaN-poisoned) statistics: neither the step count nor any parameter or moment changes.
+__global__ void adam_tick_kernel(double* hyper, const unsigned long long* skip) {
+    if (skip && *skip) return;
+    if (threadIdx.x == 0) hyper[1] = hyper[1] + 1.0;
+}
+
+__global__ void adam_dev_kernel(float* p, const float* g, float* m, float* v, long n, const double* hyper, float b1,
+                                float b2, float eps, float gscale, const unsigned long long* skip) {
+    if (skip && *skip) return;
+    const double s = hyper[1];
+    const float lr = (float)hyper[0];
+    const float bc1 = (float)(1.0 - pow((double)b1, s));
+    const float bc2 = (float)(1.0 - pow((double)b2, s));
+    const float step = lr / bc1;
+    const float bc2_sqrt = sqrtf(bc2);
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        const float gi = g[i] * gscale;
+        float mi = m[i];
+        mi = mi + (1.f - b1) * (gi - mi);
+        float vi = v[i] * b2 + (1.f - b2) * gi * gi;
+        const float denom = sqrtf(vi) / bc2_sqrt + eps;
+        p[i] = p[i] - step * (mi / denom);
+        m[i] = mi;
+        v[i] = vi;
+    }
+}
+
+// ---------------------------------------------------------------- SGD (torch.optim.SGD, single-tensor form)
+// networkFactory.py:84-89: SGD(lr, momentum 0.9, weight_decay 1e-4).  d = g + wd*p; the momentum buffer starts as a
+// copy of d on the buffer's first step, then buf = mom*buf + (1-dampening)*d; the update uses d + mom*buf (nesterov) or
+// buf.  hyper = {lr, step, initialised, snapshot} fp64 in device memory: the tick advances the step and moves the
+// buffer's "initialised" flag into the snapshot the update reads (set to 1 for the next step), so a buffer re-created
+// mid-training (flag cleared by the host) starts as torch's does, not from the global step count.
+__global__ void sgd_tick_kernel(double* hyper, const unsigned long long* skip) {
+    if (skip && *skip) return;
+    if (threadIdx.x == 0) {
+        hyper[1] = hyper[1] + 1.0;
+        hyper[3] = hyper[2];
+        hyper[2] = 1.0;
+    }
+}
+
+__global__ void sgd_dev_kernel(float* p, const float* g, float* buf, long n, const double* hyper, float mom, float damp,
+                               float wd, int nesterov, float gscale, const unsigned long long* skip) {
+    if (skip && *skip) return;
+    const float lr = (float)hyper[0];
+    const bool first = hyper[3] == 0.0;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        const float pi = p[i];
+        float d = g[i] * gscale;
+        if (wd != 0.f) d = d + wd * pi;
+        if (mom != 0.f) {
+            const float b = first ? d : buf[i] * mom + (1.f - damp) * d;
+            buf[i] = b;
+            d = nesterov ? d + mom * b : b;
+        }
+        p[i] = pi - lr * d;
+    }
+}
+}  // namespace
+
+extern "C" size_t scd_heads_bwd_accsize(int nh, int Hd, const int* od) {
+    int nout = 0;
+    for (int h = 0; h < nh; ++h) nout += od[h];
+    return (size_t)SCD_STAT_REPLICAS * (nout * Hd + nout + nh * Hd) * sizeof(double);
+}
+
+extern "C" int scd_heads_bwd_weight_finalize(double* acc, int nh, int Hd, const int* od, float* const* dw1,
+                                             float* const* db1, float* const* db0, int accumulate, float alpha, void* stream) {
+    HeadsDesc d;
+    if (!make_desc(d, nh, Hd, od)) return SCD_ERR_ARG;
+    HeadsGrad g;
+    for (int h = 0; h < 4; ++h) {
+        g.dw1[h] = h < nh ? dw1[h] : nullptr;
+        g.db1[h] = h < nh ? db1[h] : nullptr;
+        g.db0[h] = h < nh ? db0[h] : nullptr;
+    }
+    const int accsz = d.nout * Hd + d.nout + nh * Hd;
+    hipLaunchKernelGGL(heads_bwd_weight_finalize_kernel, dim3(cdiv(accsz, 256)), dim3(256), 0, (hipStream_t)stream, acc,
+                       accsz, d, g, accumulate, (double)alpha);
     SCD_RETURN_LAUNCH();
 }
+
+extern "C" int scd_adam_step(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2,
+                             float eps, float bc1, float bc2, float gscale, void* stream) {
+    hipLaunchKernelGGL(adam_kernel, dim3(ew_blocks(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, beta1,
+                       beta2, eps, bc1, sqrtf(bc2), gscale);
+    SCD_RETURN_LAUNCH();
+}
+
+extern "C" int scd_adam_step_dev(float* p, const float* g, float* m, float* v, long n, double* hyper, float beta1,
+                                 float beta2, float eps, float gscale, const unsigned long long* skip, void* stream) {
+    if (!hyper) return SCD_ERR_ARG;
+    hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, hyper, skip);
+    hipLaunchKernelGGL(adam_dev_kernel, dim3(ew_blocks(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n,
+                       (const double*)hyper, beta1, beta2, eps, gscale, skip);
+    SCD_RETURN_LAUNCH();
+}
+
+extern "C" int scd_sgd_step_dev(float* p, const float* g, float* buf, long n, double* hyper, float momentum,
+                                float dampening, float weight_decay, int nesterov, float gscale,
+                                const unsigned long long* skip, void* stream) {
+    if (!hyper || (momentum != 0.f && !buf)) return SCD_ERR_ARG;
+    hipLaunchKernelGGL(sgd_tick_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, hyper, skip);
+    hipLaunchKernelGGL(sgd_dev_kernel, dim3(ew_blocks(n)), dim3(256), 0, (hipStream_t)stream, p, g, buf, n,
+                       (const double*)hyper, momentum, dampening, weight_decay, nesterov, gscale, skip);
+    SCD_RETURN_LAUNCH();
+}
+#endif  // !SCD_F16_BUILD

@@ -6,62 +6,62 @@
 
 // fp16 compute mode (SCD_DT_F16).  The type-generic sources (conv_gemm, bn, layers, stem, pad) are compiled twice:
 // once as written (16-bit storage type h16 = __bf16, v_mfma_f32_16x16x32_bf16) and once with SCD_F16_BUILD, where h16
-// is _Float16, the MFMA is v_mfma_f32_16x16x32_f16 and every entry point gets the suffix __f16.  Those sources name
-// the 16-bit type h16 (and h16x8 / mfma_16x16x32_h16) wherever it is the build's type; __bf16 in them is always a real
-// bf16, whichever build.  A call with
-// dtype SCD_DT_F16 is forwarded by the first build to the second with dtype SCD_DT_BF16 ("the 16-bit type"), so
-// every kernel, tile shape and dispatch rule is shared and the C-ABI takes SCD_DT_F16 like any other dtype.
-#ifdef SCD_F16_BUILD
-#define scd_conv_gemm scd_conv_gemm__f16
-#define scd_conv_gemm_bnbwd scd_conv_gemm_bnbwd__f16
-#define scd_conv_gemm_res scd_conv_gemm_res__f16
-#define scd_conv_gemm_heads scd_conv_gemm_heads__f16
-#define scd_conv_gemm_heads_keep scd_conv_gemm_heads_keep__f16
-#define scd_conv_wgrad_workspace scd_conv_wgrad_workspace__f16
-#define scd_conv_wgrad_nsplit2 scd_conv_wgrad_nsplit2__f16
-#define scd_conv_wgrad_nsplit scd_conv_wgrad_nsplit__f16
-#define scd_conv_wgrad scd_conv_wgrad__f16
-#define scd_wgrad_reduce scd_wgrad_reduce__f16
-#define scd_wgrad_reduce_rows scd_wgrad_reduce_rows__f16
-#define scd_stats_collapse scd_stats_collapse__f16
-#define scd_stats_collapse_to scd_stats_collapse_to__f16
-#define scd_bn_finalize scd_bn_finalize__f16
-#define scd_bn_finalize_n scd_bn_finalize_n__f16
-#define scd_bn_bwd_finalize_n scd_bn_bwd_finalize_n__f16
-#define scd_bn_apply scd_bn_apply__f16
-#define scd_bn_bwd_reduce scd_bn_bwd_reduce__f16
-#define scd_bn_bwd_finalize scd_bn_bwd_finalize__f16
-#define scd_bn_bwd_apply scd_bn_bwd_apply__f16
-#define scd_bn_bwd_reduce2 scd_bn_bwd_reduce2__f16
-#define scd_bn_bwd_apply2 scd_bn_bwd_apply2__f16
-#define scd_pack_weights_batched scd_pack_weights_batched__f16
-#define scd_pack_weight scd_pack_weight__f16
-#define scd_im2col_stem scd_im2col_stem__f16
-#define scd_stem_pool_fwd scd_stem_pool_fwd__f16
-#define scd_stem_pool_bwd scd_stem_pool_bwd__f16
-#define scd_stem_pool_bwd_bn scd_stem_pool_bwd_bn__f16
-#define scd_heads_fwd scd_heads_fwd__f16
-#define scd_heads_bwd_accsize scd_heads_bwd_accsize__f16
-#define scd_heads_bwd scd_heads_bwd__f16
-#define scd_heads_bwd_packed scd_heads_bwd_packed__f16
-#define scd_heads_bwd_packed_split scd_heads_bwd_packed_split__f16
-#define scd_heads_sparse_bwd scd_heads_sparse_bwd__f16
-#define scd_heads_sparse_fixup scd_heads_sparse_fixup__f16
-#define scd_heads_bwd_weight_finalize scd_heads_bwd_weight_finalize__f16
-#define scd_adam_step scd_adam_step__f16
-#define scd_adam_step_dev scd_adam_step_dev__f16
-#define scd_sgd_step_dev scd_sgd_step_dev__f16
-#define scd_stem_conv_fwd scd_stem_conv_fwd__f16
-#define scd_stem_conv_wgrad_nsplit scd_stem_conv_wgrad_nsplit__f16
-#define scd_stem_conv_wgrad scd_stem_conv_wgrad__f16
-#define scd_stem_bwd_nsplit scd_stem_bwd_nsplit__f16
-#define scd_conv_dgrad_s2 scd_conv_dgrad_s2__f16
-#define scd_stem_bwd_fused scd_stem_bwd_fused__f16
-#define scd_stem_bwd_combine scd_stem_bwd_combine__f16
-#define scd_pad_channels scd_pad_channels__f16
-#endif
-
+// is _Float16, the MFMA is v_mfma_f32_16x16x32_f16 and every entry point on the list below gets the symbol name
+// name__f16.  Those sources name the 16-bit type h16 (and h16x8 / mfma_16x16x32_h16) wherever it is the build's type;
+// __bf16 in them is always a real bf16, whichever build.  A call with dtype SCD_DT_F16 is forwarded by the first build
+// to the second with dtype SCD_DT_BF16 ("the 16-bit type") by SCD_F16_FWD, the first line of each listed entry point,
+// so every kernel, tile shape and dispatch rule is shared and the C-ABI takes SCD_DT_F16 like any other dtype.
+// The second build holds the listed entry points and what they launch, nothing else: an entry point without a dtype
+// (and the kernels only it launches) sits in its file's one `#ifndef SCD_F16_BUILD` region, and the fp32 kernels are
+// named only through scd_dispatch_dtype's float arm, which that build does not have.
 #include "../../include/scdhip.h"
+
+// the entry points that take a dtype: this list is the only one (tests/test_host_cpu.py holds the SCD_F16_FWD lines
+// to it)
+#define SCD_F16_ENTRY_POINTS(X) \
+    X(scd_conv_gemm) \
+    X(scd_conv_gemm_bnbwd) \
+    X(scd_conv_gemm_res) \
+    X(scd_conv_gemm_heads) \
+    X(scd_conv_gemm_heads_keep) \
+    X(scd_conv_wgrad_nsplit2) \
+    X(scd_conv_wgrad_nsplit) \
+    X(scd_conv_wgrad) \
+    X(scd_bn_apply) \
+    X(scd_bn_bwd_reduce) \
+    X(scd_bn_bwd_apply) \
+    X(scd_bn_bwd_reduce2) \
+    X(scd_bn_bwd_apply2) \
+    X(scd_pack_weights_batched) \
+    X(scd_pack_weight) \
+    X(scd_im2col_stem) \
+    X(scd_stem_pool_fwd) \
+    X(scd_stem_pool_bwd) \
+    X(scd_stem_pool_bwd_bn) \
+    X(scd_heads_fwd) \
+    X(scd_heads_bwd) \
+    X(scd_heads_bwd_packed) \
+    X(scd_heads_bwd_packed_split) \
+    X(scd_heads_sparse_bwd) \
+    X(scd_heads_sparse_fixup) \
+    X(scd_stem_conv_fwd) \
+    X(scd_stem_conv_wgrad) \
+    X(scd_stem_bwd_fused) \
+    X(scd_conv_dgrad_s2) \
+    X(scd_stem_bwd_combine) \
+    X(scd_pad_channels)
+#ifdef SCD_F16_BUILD
+// (the preprocessor cannot write a #define per list item: the second build's definitions, and its calls from one
+// listed entry point to another, get their symbol name from this redeclaration)
+#define SCD_F16_RENAME(fn) extern "C" decltype(fn) fn __asm__(#fn "__f16");
+SCD_F16_ENTRY_POINTS(SCD_F16_RENAME)
+#define SCD_F16_FWD(fn, ...) ((void)0)
+#else
+#define SCD_F16_DECL(fn) extern "C" decltype(fn) fn##__f16;
+SCD_F16_ENTRY_POINTS(SCD_F16_DECL)
+#define SCD_F16_FWD(fn, ...) \
+    do { if (dtype == SCD_DT_F16) return fn##__f16(SCD_DT_BF16, __VA_ARGS__); } while (0)
+#endif
 
 // The fp16 build's kernels sit in an inline namespace `f16` inside each file's anonymous namespace, so their symbol
 // names (and the rocprofv3 kernel names) differ from the bf16 build's even where a kernel is not templated on the
@@ -72,45 +72,6 @@
 #else
 #define SCD_KERNEL_NS_BEGIN
 #define SCD_KERNEL_NS_END
-#endif
-
-#ifdef SCD_F16_BUILD
-#define SCD_F16_FWD(fn, ...) ((void)0)
-#else
-#define SCD_F16_DECL(fn) extern "C" decltype(fn) fn##__f16;
-SCD_F16_DECL(scd_conv_gemm)
-SCD_F16_DECL(scd_conv_gemm_bnbwd)
-SCD_F16_DECL(scd_conv_gemm_res)
-SCD_F16_DECL(scd_conv_gemm_heads)
-SCD_F16_DECL(scd_conv_gemm_heads_keep)
-SCD_F16_DECL(scd_conv_wgrad_nsplit2)
-SCD_F16_DECL(scd_conv_wgrad_nsplit)
-SCD_F16_DECL(scd_conv_wgrad)
-SCD_F16_DECL(scd_bn_apply)
-SCD_F16_DECL(scd_bn_bwd_reduce)
-SCD_F16_DECL(scd_bn_bwd_apply)
-SCD_F16_DECL(scd_bn_bwd_reduce2)
-SCD_F16_DECL(scd_bn_bwd_apply2)
-SCD_F16_DECL(scd_pack_weights_batched)
-SCD_F16_DECL(scd_pack_weight)
-SCD_F16_DECL(scd_im2col_stem)
-SCD_F16_DECL(scd_stem_pool_fwd)
-SCD_F16_DECL(scd_stem_pool_bwd)
-SCD_F16_DECL(scd_stem_pool_bwd_bn)
-SCD_F16_DECL(scd_heads_fwd)
-SCD_F16_DECL(scd_heads_bwd)
-SCD_F16_DECL(scd_heads_bwd_packed)
-SCD_F16_DECL(scd_heads_bwd_packed_split)
-SCD_F16_DECL(scd_heads_sparse_bwd)
-SCD_F16_DECL(scd_heads_sparse_fixup)
-SCD_F16_DECL(scd_stem_conv_fwd)
-SCD_F16_DECL(scd_stem_conv_wgrad)
-SCD_F16_DECL(scd_stem_bwd_fused)
-SCD_F16_DECL(scd_conv_dgrad_s2)
-SCD_F16_DECL(scd_stem_bwd_combine)
-SCD_F16_DECL(scd_pad_channels)
-#define SCD_F16_FWD(fn, ...) \
-    do { if (dtype == SCD_DT_F16) return fn##__f16(SCD_DT_BF16, __VA_ARGS__); } while (0)
 #endif
 
 // half `hi` of a 32-bit word holding two 16-bit values, as float
@@ -141,6 +102,19 @@ __device__ __forceinline__ f32x4 mfma_16x16x32_h16(h16x8 a, h16x8 b, f32x4 c) {
 }
 typedef __attribute__((ext_vector_type(4))) short s16x4;
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+
+// The one dtype dispatch of the typed entry points: f(scd_type<T>{}) with T = h16 for SCD_DT_BF16 (the build's 16-bit
+// type) or float for SCD_DT_F32, SCD_ERR_ARG for any other dtype.  The fp16 build only ever receives the 16-bit type
+// and has no float arm, so it instantiates no fp32 kernel.
+template <typename T> struct scd_type { using type = T; };
+template <typename F>
+static inline int scd_dispatch_dtype(int dtype, F&& f) {
+    if (dtype == SCD_DT_BF16) return f(scd_type<h16>{});
+#ifndef SCD_F16_BUILD
+    if (dtype == SCD_DT_F32) return f(scd_type<float>{});
+#endif
+    return SCD_ERR_ARG;
+}
 
 #define SCD_RETURN_LAUNCH() return (int)hipGetLastError()
 

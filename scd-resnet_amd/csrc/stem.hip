@@ -611,12 +611,6 @@ extern "C" int scd_stem_conv_fwd(int dtype, const float* x, const void* wpk, voi
     SCD_RETURN_LAUNCH();
 }
 
-extern "C" int scd_stem_conv_wgrad_nsplit(long M) {
-    // ~4 resident workgroups per CU, whole 64-pixel stages per split
-    long ns = std::min(2048L, std::max(1L, M / (4 * WPX)));
-    return (int)ns;
-}
-
 extern "C" int scd_stem_conv_wgrad(int dtype, const void* dy, const void* ybn, const float* coef, const float* x,
                                    float* ws, int nsplit, int N, int H, int W, int Ho, int Wo, void* stream) {
     SCD_F16_FWD(scd_stem_conv_wgrad, dy, ybn, coef, x, ws, nsplit, N, H, W, Ho, Wo, stream);
@@ -631,13 +625,6 @@ extern "C" int scd_stem_conv_wgrad(int dtype, const void* dy, const void* ybn, c
     hipLaunchKernelGGL(stem_conv_wgrad_kernel, dim3(nsplit), dim3(256), 0, (hipStream_t)stream, (const h16*)dy,
                        (const h16*)ybn, coef, x, ws, H, W, Ho, Wo, M, (int)chunk);
     SCD_RETURN_LAUNCH();
-}
-
-extern "C" int scd_stem_bwd_nsplit(void) {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-        cus = 256;
-    return 2 * cus;
 }
 
 extern "C" int scd_stem_bwd_fused(int dtype, const void* dout, const uint8_t* argmax, const void* y, const float* scale,
@@ -659,7 +646,6 @@ extern "C" int scd_stem_bwd_fused(int dtype, const void* dout, const uint8_t* ar
     SCD_RETURN_LAUNCH();
 }
 
-
 extern "C" int scd_stem_bwd_combine(int dtype, const float* tg, const void* wpk, const float* coef, float* dst,
                                     int accumulate, float alpha, void* stream) {
     SCD_F16_FWD(scd_stem_bwd_combine, tg, wpk, coef, dst, accumulate, alpha, stream);
@@ -668,3 +654,19 @@ extern "C" int scd_stem_bwd_combine(int dtype, const float* tg, const void* wpk,
                        coef, dst, accumulate, alpha);
     SCD_RETURN_LAUNCH();
 }
+
+// the split-count queries take no dtype: the first build alone holds them
+#ifndef SCD_F16_BUILD
+extern "C" int scd_stem_conv_wgrad_nsplit(long M) {
+    // ~4 resident workgroups per CU, whole 64-pixel stages per split
+    long ns = std::min(2048L, std::max(1L, M / (4 * WPX)));
+    return (int)ns;
+}
+
+extern "C" int scd_stem_bwd_nsplit(void) {
+    int dev = 0, cus = 256;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+        cus = 256;
+    return 2 * cus;
+}
+#endif  // !SCD_F16_BUILD

@@ -71,6 +71,9 @@ def test_workspace_queries():
     assert L.lib().scd_decode_workspace(2, 16384) == 2 * 16384 * 4
     od = L.int_array([1, 4, 2])
     assert L.lib().scd_heads_bwd_accsize(3, 128, od) == L.STAT_REPLICAS * (7 * 128 + 7 + 384) * 8
+    # SCD_DT_F16 is forwarded to the fp16 build, which plans the splits as for the 16-bit type
+    for args in ((64 * 1024, 128, 9, 96), (4096, 64, 9, 32)):
+        assert L.lib().scd_conv_wgrad_nsplit(L.DT_F16, *args) == L.lib().scd_conv_wgrad_nsplit(L.DT_BF16, *args) >= 1
 
 
 @pytest.mark.parametrize("name", ["centerOffsetRes10", "centerOffsetRes18", "centerOffsetRes50",
@@ -337,6 +340,33 @@ def test_no_type_macros_in_the_f16_build():
     assert not re.search(r"#\s*define\s+__bf16\b", src)
     assert not re.search(r"#\s*define\s+__builtin_amdgcn_mfma", src)
     assert "typedef _Float16 h16;" in src and "typedef __bf16 h16;" in src
+
+
+def test_f16_entry_point_list_matches_the_forwarding_lines():
+    """scd_common.h's SCD_F16_ENTRY_POINTS is the one list of the entry points the fp16 build holds: every name on it
+    forwards SCD_DT_F16 calls with exactly one SCD_F16_FWD(name, ...) line in csrc/, and no SCD_F16_FWD line names a
+    function that is not on it (that call would not link, or an fp16 call would quietly return SCD_ERR_ARG)."""
+    import glob
+    import re
+    csrc = os.path.join(REPO, "scd-resnet_amd", "csrc")
+    common = open(os.path.join(csrc, "scd_common.h")).read()
+    block = re.search(r"#define SCD_F16_ENTRY_POINTS\(X\)((?:.*\\\n)+.*\n)", common).group(1)
+    listed = re.findall(r"X\((\w+)\)", block)
+    assert len(listed) == len(set(listed)) and len(listed) >= 30
+    fwd = []
+    for path in sorted(glob.glob(os.path.join(csrc, "*.hip"))):
+        fwd += re.findall(r"SCD_F16_FWD\((\w+),", open(path).read())
+    assert sorted(fwd) == sorted(listed), sorted(set(fwd) ^ set(listed))
+    assert set(listed) <= set(header_symbols())
+    # and the built library's *__f16 exports are those names, no other
+    import shutil
+
+    import scdhip.lib as L
+    assert all(hasattr(L.lib().dll, n + "__f16") for n in listed)
+    if shutil.which("nm"):
+        out = subprocess.run(["nm", "-D", "--defined-only", L.lib().dll._name], check=True, capture_output=True,
+                             text=True).stdout
+        assert sorted(re.findall(r"\b(scd_\w+)__f16\b", out)) == sorted(listed)
 
 
 def test_profile_kernel_names():

@@ -287,12 +287,13 @@ NARROW = {"centerOffsetRes10q": [16, 16, 32, 64, 128, 64, 64, 64],
 
 
 @pytest.mark.parametrize("name", sorted(NARROW))
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16])
 def test_f11_narrow_plugins(name, dtype, golden):
     """16/32-channel layers (zero-extended to the GEMM K-stage by scd_pad_channels) and 64-wide heads against the
     reference (F11): fp32 heads 1e-3, loss 1e-4, gradient norms 2e-3 (10q, measured 6.1e-4) / 5e-3 (10h, measured
     3.2e-3; 1e-2 through round 3); bf16 within 5e-2 of the reference's heads
-    and loss (10 layers of bf16 rounding)."""
+    and loss (10 layers of bf16 rounding); fp16 (scd_heads_fwd and scd_pad_channels through the fp16 build) within a
+    quarter of that, 1.25e-2: the same ten roundings at 2^-11 instead of 2^-9."""
     import importlib
     g = golden("narrow")
     plugin = importlib.import_module("trainer.model." + name)
@@ -302,13 +303,16 @@ def test_f11_narrow_plugins(name, dtype, golden):
     m.load_state_dict(O.hash_weights(entries))
     m = m.to(DEV).train().set_compute_dtype(dtype)
     out = m(T.batch_inputs(21, 2, 256).to(DEV), decode=False)
+    tol16 = 5e-2 / 4 if dtype == torch.float16 else 5e-2
     for k in ("heatmap", "regr", "offset"):
         a = out[0][k].detach().float().cpu().numpy()
         ref = g["%s|%s" % (name, k)]
         if dtype == torch.float32:
             np.testing.assert_allclose(a, ref, rtol=1e-3, atol=1e-3, err_msg=k)
         else:
-            assert np.abs(a - ref).max() / np.abs(ref).max() < 5e-2, k
+            err = np.abs(a - ref).max() / np.abs(ref).max()
+            print("%s %s %s: %.3g of the reference's largest value" % (name, dtype, k, err))
+            assert err < tol16, k
     loss, stats = plugin.loss(out, [y.to(DEV) for y in T.batch_targets(22, 2, 64)])
     loss.mean().backward()
     torch.cuda.synchronize()
@@ -317,7 +321,9 @@ def test_f11_narrow_plugins(name, dtype, golden):
         _assert_gnorms(m, lambda k: float(g["%s|gnorm|%s" % (name, k)]), "F11 " + name,
                        2e-3 if name.endswith("q") else 5e-3)
     else:
-        np.testing.assert_allclose(loss.item(), float(g[name + "|loss"].reshape(-1)[0]), rtol=5e-2)
+        ref_loss = float(g[name + "|loss"].reshape(-1)[0])
+        print("%s %s loss: %.6g, reference %.6g" % (name, dtype, loss.item(), ref_loss))
+        np.testing.assert_allclose(loss.item(), ref_loss, rtol=tol16)
         for k, p in m.named_parameters():
             assert p.grad is not None and torch.isfinite(p.grad).all(), k
 
