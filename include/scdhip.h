@@ -390,6 +390,26 @@ int scd_slide_tiles(const uint8_t* rgb, int H, int W, int C, int tile, int strid
                     int padTB, int fix, float* out, void* workspace, void* stream);
 int scd_slide_detections(const float* decoded, int T, int K, int stride, int padLR, int padTB, int clipV, float thr,
                          int* xy, double* ratio, int* count, void* stream);
+/* ---- slide cohort quantification (test.py:148-183) ----
+ * scd_slide_samples: decoded (10, T, K) fp32 Wrapper stack, geometry as scd_slide_detections -> the valid,
+ * de-duplicated samples of one slide and their Rhr histogram; enqueued on `stream`, no host read.
+ * Candidates: score > thr and x0 <= px < x1, y0 <= py < y1 (pixel and ratio exactly as scd_slide_detections).
+ * De-duplication (radius >= 0; -1 = none), greedy by descending score, ties by ascending flat index t*K + k: a
+ * candidate is kept unless an already-kept candidate of a different clip has dx^2 + dy^2 <= radius^2 (integers).
+ * Outputs, each sized T*K, in flat (clip-major, then slot) order: xy (n,2) int32, ratio (n) float64, score (n)
+ * fp32, index (n) int32 flat indices, *count = n (device).  hist (nbins) int64 is ADDED to: bin b = floor((ratio -
+ * lo) * scale) in float64, counted when ratio is finite and 0 <= b < nbins.  counters (5) int64, ADDED to: above
+ * the threshold, valid (in the box), kept, binned, kept but not binned.
+ * SCD_ERR_ARG and no launch when T, K, stride, clipV or nbins < 1, T*K > SCD_SLIDE_SAMPLES_MAX, nbins > 1024,
+ * x1 <= x0, y1 <= y0, radius < -1 or > SCD_SLIDE_RADIUS_MAX, lo or scale is NaN, or a pointer is NULL.
+ * workspace: scd_slide_samples_workspace(T, K) bytes (0 when T*K is out of range). */
+#define SCD_SLIDE_SAMPLES_MAX 16384
+#define SCD_SLIDE_RADIUS_MAX 1048576
+size_t scd_slide_samples_workspace(int T, int K);
+int scd_slide_samples(const float* decoded, int T, int K, int stride, int padLR, int padTB, int clipV, float thr,
+                      int x0, int y0, int x1, int y1, int radius, double lo, double scale, int nbins, int* xy,
+                      double* ratio, float* score, int* index, int* count, int64_t* hist, int64_t* counters,
+                      void* workspace, void* stream);
 /* ---- building a `.d` archive (preprocess.py; datasets/preprocessor/scdManual.py:133-186,
  * datasets/argumentations.py:148-159) ----
  * scd_slide_rotate_clips: RGB slide (H,W,C>=3) u8 on the device -> out (R, nx*ny, tile, tile) fp32, nx = (W+left+

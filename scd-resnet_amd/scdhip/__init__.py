@@ -5,5 +5,6 @@ ops     tensor-level wrappers (NHWC activations, torch-owned memory and streams)
 blocks  block-granular autograd Functions (stem, BasicBlock, Bottleneck, deconv, heads, corner pool)
 loss    fused focal + masked-L1 loss Functions
 flat    flat parameter/gradient buffers, FlatAdam (torch.optim.Adam semantics), FlatDDP (RCCL)
+rhr     the Rhr histogram's two-Gaussian fit and the DFI of a slide cohort (host, numpy)
 """
 from . import lib  # noqa: F401

@@ -122,6 +122,8 @@ SIGNATURES = {
     "scd_slide_workspace": (c_size_t, [I]),
     "scd_slide_tiles": (I, [P, I, I, I, I, I, I, I, I, I, I, P, P, P]),
     "scd_slide_detections": (I, [P, I, I, I, I, I, I, F, P, P, P, P]),
+    "scd_slide_samples_workspace": (c_size_t, [I, I]),
+    "scd_slide_samples": (I, [P, I, I, I, I, I, I, F, I, I, I, I, I, D, D, I, P, P, P, P, P, P, P, P, P]),
     "scd_slide_rotate_workspace": (c_size_t, [I, I]),
     "scd_slide_rotate_clips": (I, [P, I, I, I, I, I, I, I, I, ctypes.POINTER(c_double), I, P, P, P]),
     "scd_ceval_count": (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, F, P, P]),

@@ -1601,6 +1601,38 @@ def slide_detections(decoded, stride, pad_lr, pad_tb, clip_v, threshold=0.3):
     return xy[:n], ratio[:n]
 
 
+SLIDE_SAMPLES_MAX = 16384   # SCD_SLIDE_SAMPLES_MAX: T*K slots per call
+
+
+def slide_samples(decoded, stride, pad_lr, pad_tb, clip_v, threshold, box, radius, hist, counters, lo=-0.25,
+                  scale=100.0):
+    """test.py:148-183's sample filter on the GPU (scd_slide_samples): decoded (10, T, K) Wrapper stack
+    -> (xy (T*K,2) int32, ratio (T*K,) float64, score (T*K,) float32, index (T*K,) int32, count (1,) int32), all on
+    the device and with no host read: the first count[0] entries are the samples with score > threshold whose
+    pixel lies in box = (x0, y0, x1, y1), greedily de-duplicated across clips within `radius` pixels (-1: not at
+    all), in the reference's clip-major order.  hist (nbins,) int64 and counters (5,) int64 are the caller's device
+    buffers and are added to: bin floor((ratio - lo) * scale); counters = above the threshold, valid, kept, binned,
+    kept but not binned.  T*K <= SLIDE_SAMPLES_MAX."""
+    _need_gpu(decoded, hist, counters)
+    d = decoded.float().contiguous()
+    _, T, K = d.shape
+    if hist.dtype != torch.int64 or counters.dtype != torch.int64 or hist.dim() != 1 or counters.numel() != 5 or \
+            not hist.is_contiguous() or not counters.is_contiguous():
+        raise RuntimeError("slide_samples: hist (nbins,) and counters (5,) contiguous int64 device buffers expected")
+    x0, y0, x1, y1 = [int(v) for v in box]
+    dev = d.device
+    xy = torch.empty(T * K, 2, dtype=torch.int32, device=dev)
+    ratio = torch.empty(T * K, dtype=torch.float64, device=dev)
+    score = torch.empty(T * K, dtype=torch.float32, device=dev)
+    index = torch.empty(T * K, dtype=torch.int32, device=dev)
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    ws = torch.empty(max(8, L.lib().scd_slide_samples_workspace(T, K)), dtype=torch.uint8, device=dev)
+    L.call("scd_slide_samples", ptr(d), T, K, stride, pad_lr, pad_tb, clip_v, float(threshold), x0, y0, x1, y1,
+           int(radius), float(lo), float(scale), hist.numel(), ptr(xy), ptr(ratio), ptr(score), ptr(index),
+           ptr(count), ptr(hist), ptr(counters), ptr(ws), stream())
+    return xy, ratio, score, index, count
+
+
 def slide_rotate_geometry(H, W, margins, tile):
     """(nx, ny) clips of a slide cut by slide_rotate_clips: the margin-padded frame over the tile size."""
     l, t, r, b = [int(m) for m in margins]

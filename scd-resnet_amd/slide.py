@@ -56,11 +56,17 @@ def tiles(rgb, device=None):
 
 
 @torch.no_grad()
-def analyseArray(model, rgb, batch=BATCHSIZE):
-    from scdhip import ops
+def decodeArray(model, rgb, batch=BATCHSIZE):
+    """The slide's clips through the model in batches: ((10, T, K) decoded stack on the device, geometry)."""
     clips, g = tiles(rgb)
     decoded = [model(clips[i:i + batch]) for i in range(0, clips.shape[0], batch)]
-    dec = torch.cat(decoded, 1)
+    return torch.cat(decoded, 1), g
+
+
+@torch.no_grad()
+def analyseArray(model, rgb, batch=BATCHSIZE):
+    from scdhip import ops
+    dec, g = decodeArray(model, rgb, batch)
     xy, ratio = ops.slide_detections(dec, INPUTSIZE - 2 * PADDINGSIZE, g["padLR"], g["padTB"], g["clipV"], THRESHOLD)
     xy, ratio = xy.cpu().tolist(), ratio.cpu().tolist()
     return [[p[0], p[1], r] for p, r in zip(xy, ratio)]
@@ -72,15 +78,24 @@ def analyseImages(model, fullPath):
     return analyseArray(model, np.array(Image.open(fullPath)))
 
 
-def main(argv):
+@torch.no_grad()
+def analyseSamples(model, rgb, box, radius, hist, counters, batch=BATCHSIZE):
+    """The valid, de-duplicated samples of one slide (ops.slide_samples): tiling, batching and
+    concatenation as analyseArray, then the box filter, the greedy cross-clip de-duplication within `radius` pixels
+    (-1: none) and the Rhr histogram on the device.  box = (x0, y0, x1, y1), or None for the slide's own 0 0 W H.
+    hist / counters are the caller's device buffers and are added to.  Returns device tensors (xy, ratio, score,
+    index, count) and reads nothing back: the first count[0] entries are the samples."""
+    from scdhip import ops
+    dec, g = decodeArray(model, rgb, batch)
+    if box is None:
+        box = (0, 0, rgb.shape[1], rgb.shape[0])
+    return ops.slide_samples(dec, INPUTSIZE - 2 * PADDINGSIZE, g["padLR"], g["padTB"], g["clipV"], THRESHOLD, box,
+                             radius, hist, counters)
+
+
+def load_wrapper(arch, ckpt, evalMode, foldMode):
+    """The inference Wrapper for a state dict or a TorchScript archive, on the GPU."""
     import importlib
-    foldMode = "-fold" in argv
-    evalMode = "-eval" in argv or foldMode
-    argv = [a for a in argv if a not in ("-eval", "-fold")]
-    if len(argv) < 3:
-        print(__doc__)
-        return 2
-    arch, ckpt, images = argv[0], argv[1], argv[2:]
     import zipfile
     if zipfile.is_zipfile(ckpt) and any(n.endswith("constants.pkl") for n in zipfile.ZipFile(ckpt).namelist()):
         # a TorchScript archive (test.py:145 loads the trace.py output): ours replays scd::centernet_decode, a
@@ -97,6 +112,18 @@ def main(argv):
             from scdhip import infer
             model = infer.fold(model)
         wrapper = importlib.import_module("trainer.wrappers.centerOffsetResidual").Wrapper(model)
+    return wrapper
+
+
+def main(argv):
+    foldMode = "-fold" in argv
+    evalMode = "-eval" in argv or foldMode
+    argv = [a for a in argv if a not in ("-eval", "-fold")]
+    if len(argv) < 3:
+        print(__doc__)
+        return 2
+    arch, ckpt, images = argv[0], argv[1], argv[2:]
+    wrapper = load_wrapper(arch, ckpt, evalMode, foldMode)
     for img in images:
         for d in analyseImages(wrapper, img):
             print("%s\t%d\t%d\t%.6f" % (img, d[0], d[1], d[2]))
