@@ -377,6 +377,25 @@ int scd_render_center_targets(const float* locs, const int* counts, int B, int K
 size_t scd_augment_workspace(int B);
 int scd_augment_tiles(const float* in, float* out, int B, int H, int W, const uint8_t* flips, const float* jitter,
                       const float* noise, float noise_sv, unsigned long long seed, void* workspace, void* stream);
+/* Random-angle rotation of a training batch (the step datasets/scds/scdx16p100.py:443-451 holds switched off):
+ * out[b] = argumentations.rotate(in[b], angle_b, MirrorPadding, Bilinear) (datasets/argumentations.py:148-159) for
+ * in, out (B,H,W) fp32 and cs (B,2) fp64 on the device = (cos, sin) of each tile's angle in radians: torch-'reflect'
+ * padding to the diagonal (ceil(sqrt(W^2 + H^2) / 2 - dim / 2) per axis), torchvision's tensor rotate about the
+ * padded frame's centre (bilinear, zeros outside the frame, align_corners = False), the centre crop; nothing padded
+ * or rotated is materialised.  Source coordinates in fp64, the two weights and three lerps in fp32 without
+ * contraction, in scd_slide_rotate_clips' order: at angle 0 out equals in bit for bit.  SCD_ERR_ARG and no launch
+ * for a NULL pointer, in == out, B < 1, H < 2, W < 4, W % 4 != 0, a diagonal padding >= its dimension, or
+ * H*W >= 2^31.  scd_rotate_tiles_mapped is the same with the thread-to-pixel mapping named (SCD_ERR_ARG for an
+ * unknown one; every mapping gives the same bits): tools/rotate_bench.py times them, scd_rotate_tiles uses
+ * SCD_ROTATE_MAP_DEFAULT. */
+#define SCD_ROTATE_MAP_ROW 0     /* a wave = 64 consecutive quads of the flattened tile (256 pixels of a row) */
+#define SCD_ROTATE_MAP_64X4 1    /* a wave = 64 pixels x 4 rows, a workgroup 64 x 16 */
+#define SCD_ROTATE_MAP_32X8 2    /* a wave = 32 pixels x 8 rows, a workgroup 32 x 32 */
+#define SCD_ROTATE_MAP_16X16 3   /* a wave = 16 pixels x 16 rows, a workgroup 16 x 64 */
+#define SCD_ROTATE_MAP_DEFAULT SCD_ROTATE_MAP_32X8
+int scd_rotate_tiles(const float* in, float* out, int B, int H, int W, const double* cs, void* stream);
+int scd_rotate_tiles_mapped(const float* in, float* out, int B, int H, int W, const double* cs, int mapping,
+                            void* stream);
 /* ---- whole-slide tiled inference (test.py:19-135) ----
  * scd_slide_tiles: RGB slide (H,W,C>=3) u8 on the device -> out (clipH*clipV, 1, tile, tile) fp32 clips, x-major,
  * grey = round(0.1140 c0 + 0.5870 c1 + 0.2989 c2) (float64), torch-'reflect' padding by padLR / padTB, the

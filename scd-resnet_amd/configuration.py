@@ -2,10 +2,12 @@
 
 Same default keys and the same overlay rule: a JSON config replaces only keys that already
 exist (configuration.py:150-153); string values may reference other keys as `{key}` format
-fields.  Two keys are added: ``computeDtype`` ("bf16" | "fp16" | "fp32"), the MFMA precision of the
-HIP path (the reference trains in fp32 without AMP), and ``stepGraph`` (true | false, default false):
+fields.  Three keys are added: ``computeDtype`` ("bf16" | "fp16" | "fp32"), the MFMA precision of the
+HIP path (the reference trains in fp32 without AMP), ``stepGraph`` (true | false, default false):
 replay the training step as a captured HIP graph after two eager steps (single-process runs;
-scdhip/graph.py -- measured slower than eager issue on ROCm 7).
+scdhip/graph.py -- measured slower than eager issue on ROCm 7), and ``rotateAugmentation``
+(degrees, default 0.0 = off): the `.d` dataset plugins rotate every training tile and its labels by an angle
+drawn uniformly from [-value, value] (the reference holds this step switched off).
 """
 import os
 
@@ -43,6 +45,7 @@ class Configuration:
         c["useGPU"] = False
         c["computeDtype"] = "bf16"
         c["stepGraph"] = False
+        c["rotateAugmentation"] = 0.0
         self.config = c
 
     # -- formatted / plain accessors (configuration.py:46-146)
@@ -81,6 +84,7 @@ class Configuration:
     dirDataSplitProfile = property(lambda s: s._fmt("dirDataSplitProfile"))
     computeDtype = property(lambda s: s.config["computeDtype"])
     stepGraph = property(lambda s: bool(s.config["stepGraph"]))
+    rotateAugmentation = property(lambda s: float(s.config["rotateAugmentation"]))
 
     def useGPU(self):
         # a bound method, hence always truthy when tested without a call (reference quirk)

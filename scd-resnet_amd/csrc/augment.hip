@@ -13,7 +13,13 @@
 // Per-pixel noise comes from the caller (a device tensor: parity tests replay the reference's draws) or from
 // a counter-based generator (splitmix64 of (seed, tile, pixel) -> Box-Muller), so the batch path needs no
 // host random numbers.
-#include "scd_common.h"
+//
+// scd_rotate_tiles: the per-sample random rotation the reference wrote as the last step of SCD.argumentation and left
+// switched off (scdx16p100.py:443-451): out[b] = argumentations.rotate(in[b], angle_b, MirrorPadding, Bilinear)
+// (argumentations.py:148-159: torch-'reflect' padding to the diagonal, torchvision's tensor rotate about the padded
+// frame's centre, the centre crop) in one launch that materialises neither the padded nor the rotated frame -- the
+// arithmetic of preprocess.hip's slide rotation (rotate_taps.h) with a single reflection and one angle per tile.
+#include "rotate_taps.h"
 
 #pragma clang fp contract(off)
 
@@ -129,6 +135,81 @@ __global__ __launch_bounds__(AUG_THREADS) void aug_apply_kernel(AugArgs a) {
     }
 }
 
+struct RotTiles {
+    const float* in;
+    float* out;
+    const double* cs;       // (B,2): cos, sin of each tile's angle
+    int B, H, W;
+    int lp, tp;             // rotate()'s diagonal padding
+    long units;             // workgroup footprints per tile
+};
+
+// One thread = four adjacent output pixels.  The 256 threads of a workgroup cover a footprint of PW quads x 256 / PW
+// rows (PW = 1 << LOGPW), so a wave covers 4 PW pixels x 64 / PW rows; LOGPW < 0: 256 consecutive quads of the
+// flattened tile (a wave = 256 pixels of one row when W >= 256).  Footprints stride over grid.x, tiles over grid.y.
+template <int LOGPW>
+__global__ __launch_bounds__(AUG_THREADS) void rotate_tiles_kernel(RotTiles a) {
+    const int tid = threadIdx.x;
+    const int w4 = a.W >> 2;
+    const int Wq = a.W + 2 * a.lp, Hq = a.H + 2 * a.tp;
+    const double mx = 0.5 * (double)(Wq - 1), my = 0.5 * (double)(Hq - 1);
+    const long hw = (long)a.H * a.W;
+    for (int b = blockIdx.y; b < a.B; b += gridDim.y) {
+        const double ca = a.cs[(long)b * 2], sa = a.cs[(long)b * 2 + 1];
+        const float* src = a.in + (long)b * hw;
+        float* dst = a.out + (long)b * hw;
+        for (long u = blockIdx.x; u < a.units; u += gridDim.x) {
+            int i, q;
+            if (LOGPW < 0) {
+                const long e = u * AUG_THREADS + tid;
+                i = (int)(e / w4);
+                q = (int)(e - (long)i * w4);
+            } else {
+                constexpr int LW = LOGPW < 0 ? 0 : LOGPW, PW = 1 << LW, PH = AUG_THREADS >> LW;
+                const int ux = (w4 + PW - 1) >> LW;
+                const long uy = u / ux;
+                i = (int)uy * PH + (tid >> LW);
+                q = (int)(u - uy * ux) * PW + (tid & (PW - 1));
+            }
+            if (i >= a.H || q >= w4) continue;
+            const double yc = (double)(i + a.tp) - my;
+            float res[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const double xc = (double)(q * 4 + k + a.lp) - mx;
+                const double sx = (ca * xc - sa * yc) + mx;
+                const double sy = (sa * xc + ca * yc) + my;
+                int x0, y0;
+                float wx, wy;
+                rot_cell(sx, sy, x0, y0, wx, wy);
+                // taps outside the padded frame are grid_sample's zeros; inside it, -W < tap - lp < 2W - 1 as lp < W
+                const bool cin0 = x0 >= 0 && x0 < Wq, cin1 = x0 + 1 >= 0 && x0 + 1 < Wq;
+                const bool rin0 = y0 >= 0 && y0 < Hq, rin1 = y0 + 1 >= 0 && y0 + 1 < Hq;
+                const int c0 = cin0 ? reflect_idx(x0 - a.lp, a.W) : 0, c1 = cin1 ? reflect_idx(x0 + 1 - a.lp, a.W) : 0;
+                const long r0 = (long)(rin0 ? reflect_idx(y0 - a.tp, a.H) : 0) * a.W;
+                const long r1 = (long)(rin1 ? reflect_idx(y0 + 1 - a.tp, a.H) : 0) * a.W;
+                const float v00 = rin0 && cin0 ? src[r0 + c0] : 0.0f, v01 = rin0 && cin1 ? src[r0 + c1] : 0.0f;
+                const float v10 = rin1 && cin0 ? src[r1 + c0] : 0.0f, v11 = rin1 && cin1 ? src[r1 + c1] : 0.0f;
+                res[k] = rot_lerp(v00, v01, v10, v11, wx, wy);
+            }
+            *(float4*)(dst + (long)i * a.W + q * 4) = make_float4(res[0], res[1], res[2], res[3]);
+        }
+    }
+}
+
+template <int LOGPW>
+int rotate_tiles_launch(RotTiles a, hipStream_t st) {
+    if (LOGPW < 0) {
+        a.units = ((long)a.H * (a.W >> 2) + AUG_THREADS - 1) / AUG_THREADS;
+    } else {
+        constexpr int LW = LOGPW < 0 ? 0 : LOGPW, PW = 1 << LW, PH = AUG_THREADS >> LW;
+        a.units = (long)(((a.W >> 2) + PW - 1) / PW) * ((a.H + PH - 1) / PH);
+    }
+    const dim3 grid((unsigned)min(a.units, 1L << 20), (unsigned)min(a.B, 65535));
+    hipLaunchKernelGGL(rotate_tiles_kernel<LOGPW>, grid, dim3(AUG_THREADS), 0, st, a);
+    SCD_RETURN_LAUNCH();
+}
+
 }  // namespace
 
 extern "C" size_t scd_augment_workspace(int B) { return (size_t)B * AUG_SLICES * 2 * sizeof(double); }
@@ -147,4 +228,26 @@ extern "C" int scd_augment_tiles(const float* in, float* out, int B, int H, int 
     int bx = (int)min(64L, (hw / 4 + AUG_THREADS - 1) / AUG_THREADS);
     hipLaunchKernelGGL(aug_apply_kernel, dim3(bx, B), dim3(AUG_THREADS), 0, st, a);
     SCD_RETURN_LAUNCH();
+}
+
+extern "C" int scd_rotate_tiles_mapped(const float* in, float* out, int B, int H, int W, const double* cs, int mapping,
+                                       void* stream) {
+    if (!in || !out || !cs || in == out || B < 1 || H < 2 || W < 4 || (W & 3) || (long)H * W >= (1L << 31))
+        return SCD_ERR_ARG;
+    const double radius = sqrt((double)W * W + (double)H * H) / 2.0;           // argumentations.py:153-155
+    const long lp = (long)ceil(radius - 0.5 * W), tp = (long)ceil(radius - 0.5 * H);
+    if (lp >= W || tp >= H) return SCD_ERR_ARG;                                // 'reflect' needs pad < size
+    const RotTiles a{in, out, cs, B, H, W, (int)lp, (int)tp, 0};
+    hipStream_t st = (hipStream_t)stream;
+    switch (mapping) {
+        case SCD_ROTATE_MAP_ROW: return rotate_tiles_launch<-1>(a, st);
+        case SCD_ROTATE_MAP_64X4: return rotate_tiles_launch<4>(a, st);
+        case SCD_ROTATE_MAP_32X8: return rotate_tiles_launch<3>(a, st);
+        case SCD_ROTATE_MAP_16X16: return rotate_tiles_launch<2>(a, st);
+    }
+    return SCD_ERR_ARG;
+}
+
+extern "C" int scd_rotate_tiles(const float* in, float* out, int B, int H, int W, const double* cs, void* stream) {
+    return scd_rotate_tiles_mapped(in, out, B, H, W, cs, SCD_ROTATE_MAP_DEFAULT, stream);
 }

@@ -10,7 +10,7 @@
 // rotated slide is ever materialised; the plane of a 2048 x 3072 slide is 25 MB, so the taps are served from the
 // L2 / Infinity Cache, and neighbouring lanes read neighbouring plane pixels at the +-15 degrees the preprocessor
 // draws), the interpolation in fp32, one float4 store.
-#include "scd_common.h"
+#include "rotate_taps.h"
 
 #include <math.h>
 
@@ -42,13 +42,6 @@ __global__ __launch_bounds__(RC_THREADS) void slide_grey_kernel(const uint8_t* r
     }
 }
 
-// torch 'reflect' (no edge repeat); valid for -n < i < 2n - 1
-__device__ __forceinline__ int reflect_idx(int i, int n) {
-    if (i < 0) i = -i;
-    if (i >= n) i = 2 * (n - 1) - i;
-    return i;
-}
-
 // rotated-frame tap -> raw column / row, or -1 when the tap is outside the frame (grid_sample's zeros padding)
 __device__ __forceinline__ int tap_index(int tap, int nq, int pad2, int np, int pad1, int n) {
     if (tap < 0 || tap >= nq) return -1;
@@ -77,16 +70,14 @@ __global__ __launch_bounds__(RC_THREADS) void slide_rotate_kernel(RotGeom g, flo
             const double xc = (double)(cx * g.tile + j0 + k + g.lp) - mx;
             const double sx = (ca * xc - sa * yc) + mx;
             const double sy = (sa * xc + ca * yc) + my;
-            const double fx = floor(sx), fy = floor(sy);
-            const float wx = (float)(sx - fx), wy = (float)(sy - fy);
-            const int x0 = (int)fx, y0 = (int)fy;
+            int x0, y0;
+            float wx, wy;
+            rot_cell(sx, sy, x0, y0, wx, wy);
             const int c0 = tap_index(x0, g.Wq, g.lp, g.Wp, g.l, g.W), c1 = tap_index(x0 + 1, g.Wq, g.lp, g.Wp, g.l, g.W);
             const int r0 = tap_index(y0, g.Hq, g.tp, g.Hp, g.t, g.H), r1 = tap_index(y0 + 1, g.Hq, g.tp, g.Hp, g.t, g.H);
             const float v00 = tap_value(g, r0, c0), v01 = tap_value(g, r0, c1);
             const float v10 = tap_value(g, r1, c0), v11 = tap_value(g, r1, c1);
-            const float top = v00 * (1.0f - wx) + v01 * wx;
-            const float bot = v10 * (1.0f - wx) + v11 * wx;
-            res[k] = top * (1.0f - wy) + bot * wy;
+            res[k] = rot_lerp(v00, v01, v10, v11, wx, wy);
         }
         *reinterpret_cast<float4*>(dst + (long)i * g.tile + j0) = make_float4(res[0], res[1], res[2], res[3]);
     }

@@ -1570,6 +1570,41 @@ def augment_tiles(tiles, flips=None, jitter=None, noise=None, noise_sv=0.0, seed
     return out.view(shape)
 
 
+ROTATE_MAPS = {"row": 0, "64x4": 1, "32x8": 2, "16x16": 3}      # SCD_ROTATE_MAP_*: a wave's pixels x rows
+
+
+def rotate_tiles(tiles, angles_deg, out=None, mapping=None):
+    """The random-angle rotation of a training batch on the GPU (scd_rotate_tiles; the step scdx16p100.py:443-451
+    holds switched off): out[b] = argumentations.rotate(tiles[b], angles_deg[b], MirrorPadding, Bilinear)
+    (argumentations.py:148-159), positive angles counter-clockwise as torchvision's.  tiles (B,1,H,W) or (B,H,W)
+    fp32 on the device, angles_deg B host numbers; the cosines and sines are taken here on the host in float64, from
+    the expression slide_rotate_clips' library side uses (angle * pi / 180).  The rotation is torchvision's tensor
+    rotate restated, as in slide_rotate_clips: equality with real torchvision has not been measured.  Returns a new
+    tensor, or `out` (fp32, contiguous, not `tiles`) viewed in the tiles' shape.  mapping: a ROTATE_MAPS key, for
+    tools/rotate_bench.py; every mapping gives the same bits."""
+    _need_gpu(tiles, out)
+    if tiles.dtype != torch.float32:
+        raise RuntimeError("rotate_tiles: fp32 tiles expected, got %s" % tiles.dtype)
+    shape = tiles.shape
+    if tiles.dim() not in (3, 4) or (tiles.dim() == 4 and shape[1] != 1):
+        raise RuntimeError("rotate_tiles: (B,H,W) or (B,1,H,W) expected, one channel per tile")
+    t = tiles.contiguous()
+    B, H, W = shape[0], shape[-2], shape[-1]
+    ang = [float(a) * math.pi / 180.0 for a in angles_deg]
+    if len(ang) != B:
+        raise RuntimeError("rotate_tiles: %d angles for %d tiles" % (len(ang), B))
+    if out is None:
+        out = torch.empty_like(t)
+    elif out.dtype != torch.float32 or out.numel() != t.numel() or not out.is_contiguous():
+        raise RuntimeError("rotate_tiles: out must be a contiguous fp32 tensor of the tiles' size")
+    cs = torch.tensor([[math.cos(a), math.sin(a)] for a in ang], dtype=torch.float64).reshape(-1, 2).to(t.device)
+    if mapping is None:
+        L.call("scd_rotate_tiles", ptr(t), ptr(out), B, H, W, ptr(cs), stream())
+    else:
+        L.call("scd_rotate_tiles_mapped", ptr(t), ptr(out), B, H, W, ptr(cs), ROTATE_MAPS[mapping], stream())
+    return out.view(shape)
+
+
 def slide_tiles(rgb, tile, stride, clip_h, clip_v, pad_lr, pad_tb, fix):
     """test.py:19-87 on the GPU (scd_slide_tiles): RGB slide (H,W,C) uint8 -> (clip_h*clip_v, 1, tile, tile)
     normalised float32 clips, x-major."""

@@ -28,6 +28,9 @@ and the targets as scd_render_center_targets, batched over a whole training batc
 reference does both per sample in PyTorch.  Stored bounds are never mutated (the reference's CPU path flips
 and truncates them in place, :424-429, :523-525).  A smaller-than-canonical archive (tests) indexes only the
 positions it holds.  The reference's CUDA path pins cuda:0 (:316-356); here the device is the caller's.
+The random-angle rotation the reference wrote as the augmentation's last step and left switched off (:443-486) runs
+here when the configuration key rotateAugmentation (maximum absolute angle, degrees) is above 0: scd_rotate_tiles
+on the augmented tiles, SCD.rotateLocs on the flipped labels; the validation set is never rotated.
 """
 import io
 import json
@@ -232,34 +235,78 @@ class SCD(Dataset):
             locs[:, 5] = -locs[:, 5]
         return locs
 
+    @staticmethod
+    def rotateLocs(locs, angle, size=HEATMAPSIZE):
+        """The label half of the rotation the reference holds switched off (scdx16p100.py:455-483): every row and
+        its eight mirror images across the map's edges, in the reference's order (:459-471), turned by `angle`
+        degrees about (size // 2 - 0.5, size // 2 - 0.5) with the reference's float32 rotateCoordinates (restated
+        in datasets.preprocessor.scdManual), then the rows whose truncated centre (int(), toward zero) lies in
+        [0, size) on both axes, in order.  One deviation: a centre at distance 0 from the rotation centre stays
+        where it is (the reference divides 0 / 0 there and then fails in int(nan))."""
+        from datasets.preprocessor.scdManual import rotateCoordinates
+        locs = (locs.numpy() if torch.is_tensor(locs) else np.asarray(locs)).astype(np.float32).reshape(-1, 8)
+        if not len(locs):
+            return locs
+        far = np.float32(2 * size - 1)
+        rep = np.repeat(locs[:, None, :], 9, axis=1)
+        ctx, cty = locs[:, 0], locs[:, 1]
+        xs = (ctx, far - ctx, np.float32(-1) - ctx)
+        ys = (cty, np.float32(-1) - cty, far - cty)
+        for k in range(9):
+            kx, ky = divmod(k, 3)
+            rep[:, k, 0], rep[:, k, 1] = xs[kx], ys[ky]
+            if kx:
+                rep[:, k, 2], rep[:, k, 4] = -locs[:, 2], -locs[:, 4]
+            if ky:
+                rep[:, k, 3], rep[:, k, 5] = -locs[:, 3], -locs[:, 5]
+        rep = rep.reshape(-1, 8)
+        half = size // 2
+        still = (rep[:, 0] + np.float32(0.5 - half) == 0) & (rep[:, 1] + np.float32(0.5 - half) == 0)
+        out = rotateCoordinates(torch.from_numpy(rep.copy()), half, half, angle).numpy()
+        out[still, :2] = rep[still, :2]
+        cx, cy = np.trunc(out[:, 0]), np.trunc(out[:, 1])
+        return out[(cx >= 0) & (cx < size) & (cy >= 0) & (cy < size)]
+
     def _draws(self, B):
         """The reference's random draws per sample, in its order: two numpy uniforms (flips), one torch normal
-        (jitter); the per-pixel noise comes from the device generator keyed by one torch-drawn seed."""
+        (jitter); the per-pixel noise comes from the device generator keyed by one torch-drawn seed.  With the
+        configuration's rotateAugmentation R > 0 a third numpy uniform per sample, after the two flip draws:
+        angle = u * 2R - R (the reference's switched-off `uniform() * 4 - 2` at R = 2, scdx16p100.py:449);
+        angles is None when R is 0 and no draw is made."""
+        from configuration import defaultConfig
+        R = defaultConfig.rotateAugmentation
         flips = np.zeros((B, 2), np.uint8)
         jit = np.zeros(B, np.float32)
+        angles = np.zeros(B, np.float64) if R > 0 else None
         for b in range(B):
             flips[b, 0] = np.random.uniform() > 0.5
             flips[b, 1] = np.random.uniform() > 0.5
+            if R > 0:
+                angles[b] = np.random.uniform() * (2 * R) - R
             jit[b] = np.float32(1) + np.float32(JITTERSV) * torch.randn(1).numpy()[0]
         seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-        return flips, jit, seed
+        return flips, jit, seed, angles
 
     def gpu_batch(self, indices, device=None):
         """A training batch augmented and target-rendered on the GPU in two launches each (scd_augment_tiles,
         scd_render_center_targets): {"xs": [(B,1,S,S)], "ys": [heat, mask, regr, inds]} on the device, the
-        reference's __getitem__ stacked over `indices` (positions in the shuffled order)."""
+        reference's __getitem__ stacked over `indices` (positions in the shuffled order).  With the configuration's
+        rotateAugmentation > 0, scd_rotate_tiles and rotateLocs follow the augmentation and the flips."""
         from scdhip import ops
         dev = device or self.device
         if 0 in indices:
             shuffle(self.order)      # the reference reshuffles when index 0 is fetched (scdx16p100.py:302-305)
         ids = [self.order[i] for i in indices]
         B = len(ids)
-        flips, jit, seed = self._draws(B)
+        flips, jit, seed, angles = self._draws(B)
         tiles = torch.stack([self.samples[i] for i in ids]).to(dev)
         xs = ops.augment_tiles(tiles, torch.from_numpy(flips).to(dev), torch.from_numpy(jit).to(dev), None,
                                NOISESV, seed)
-        l, n = _pack_locs([self.flipLocs(self.bounds[i], flips[b, 0], flips[b, 1]) for b, i in enumerate(ids)],
-                          trunc=True)
+        rows = [self.flipLocs(self.bounds[i], flips[b, 0], flips[b, 1]) for b, i in enumerate(ids)]
+        if angles is not None:      # rotateAugmentation > 0: the rotation comes last, as the reference wrote it
+            xs = ops.rotate_tiles(xs, angles)
+            rows = [self.rotateLocs(r, a) for r, a in zip(rows, angles)]
+        l, n = _pack_locs(rows, trunc=True)
         ys = ops.render_center_targets(torch.from_numpy(l).to(dev), torch.from_numpy(n).to(dev), HEATMAPSIZE,
                                        THRESHOLDIOU)
         return {"xs": [xs], "ys": ys}
