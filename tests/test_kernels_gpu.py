@@ -27,6 +27,26 @@ def nchw(t):
 
 
 TOL = {torch.float32: 1e-4, torch.bfloat16: 3e-2, torch.float16: 1e-2}
+# four times the largest error observed per dtype (below), never looser than 1e-3
+SQ_TOL = {torch.float32: 7.5e-6, torch.bfloat16: 2.2e-6, torch.float16: 2.3e-6}
+
+
+def assert_sum_squares(got, yd, dtype, what):
+    """Per-channel sum of y^2 from a producer's epilogue (the half of the statistics every training invstd rests on)
+    against the float64 sum of the reference output squared.  The terms are non-negative, so the bound is relative.
+
+    Observed on an MI355X, the maximum over channels and over every case that reaches this function (CONV_CASES,
+    LARGE_CONV_CASES, PP2_ROWS_CASES, LAYER1_CASES, L1_WGRAD_CASES and the direct stem): fp32 1.87e-6, bf16 5.48e-7,
+    fp16 5.74e-7, all three at (1, 256, 8, 8, 512, 3, 2, 1) (16 pixels per channel, K = 2304); the stem 9.1e-9 at most.
+    The sums are taken from the fp32 accumulators before the output is rounded, so the 16-bit figures are no larger
+    than fp32's; what is left is the fp32 rounding of the reference convolution and of the partial sums.  At the
+    largest shape one lost 256-pixel tile of 65,536 pixels per channel is 4e-3."""
+    want = (yd * yd).sum((0, 2, 3))
+    err = ((got.double() - want).abs() / want).max().item()
+    print("sum y^2 max relative error %s %s: %.3g" % (what, dtype, err))
+    assert err <= SQ_TOL[dtype], (what, err)
+
+
 CONV_CASES = [  # N, Cin, H, W, Cout, k, stride, pad
     (2, 64, 16, 16, 64, 3, 1, 1),
     (2, 64, 16, 16, 128, 3, 2, 1),
@@ -45,6 +65,9 @@ CONV_CASES = [  # N, Cin, H, W, Cout, k, stride, pad
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("case", CONV_CASES)
 def test_conv_fwd_dgrad_wgrad(case, dtype):
+    """Forward (+ the epilogue's BN sums), input gradient and weight gradient against torch fp32.  The sum of y^2 is
+    held to SQ_TOL: four times the largest error observed (fp32 1.87e-6, bf16 5.48e-7, fp16 5.74e-7; see
+    assert_sum_squares)."""
     from scdhip import ops
     N, Cin, H, W, Cout, k, s, p = case
     g = torch.Generator().manual_seed(hash(case) & 0xFFFF)
@@ -68,12 +91,82 @@ def test_conv_fwd_dgrad_wgrad(case, dtype):
     st = stats.view(-1, 2, Cout).sum(0).cpu()
     yd = yr.detach().double()
     np.testing.assert_allclose(st[0].numpy(), yd.sum((0, 2, 3)).numpy(), rtol=1e-3, atol=1e-2 * yd.numel() ** 0.5)
+    assert_sum_squares(st[1], yd, dtype, "conv %s" % (case,))
     dyg = nhwc(dy, dtype)
     dx = ops.conv_dgrad(dyg, ops.pack_weight(wd, dtype, 1), Cin, H, W, k, k, s, p)
     assert rel_err(nchw(dx), xr.grad) < TOL[dtype]
     dw = torch.zeros_like(wd)
     ops.conv_wgrad(dyg, xg, k, k, s, p, dw, (Cin * k * k, k * k, 1), accumulate=False)
     assert rel_err(dw, wr.grad) < TOL[dtype] * 3
+
+
+def _four_tap_conv(x, idx, sign, k, s, p):
+    """float64 convolution of x (N, Ci, H, W) with weights that have four taps of +-1 per output channel (flat tap
+    positions idx (Co, 4) over Ci * k * k), as four gathers: no product, no summation order."""
+    N, Ci, H, W = x.shape
+    Co = idx.shape[0]
+    Ho, Wo = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
+    xp = F.pad(x, (p, p, p, p))
+    dev = x.device
+    n = torch.arange(N, device=dev).view(N, 1, 1, 1)
+    ho = torch.arange(Ho, device=dev).view(1, 1, Ho, 1) * s
+    wo = torch.arange(Wo, device=dev).view(1, 1, 1, Wo) * s
+    y = torch.zeros(N, Co, Ho, Wo, dtype=torch.float64, device=dev)
+    for t in range(4):
+        ci = (idx[:, t] // (k * k)).view(1, Co, 1, 1)
+        kh = (idx[:, t] % (k * k) // k).view(1, Co, 1, 1)
+        kw = (idx[:, t] % k).view(1, Co, 1, 1)
+        y += sign[:, t].view(1, Co, 1, 1) * xp[n, ci, ho + kh, wo + kw]
+    return y
+
+
+EXACT_STAT_CASES = [
+    # the family each shape reaches, from the dispatch order in conv_gemm.hip (conv_gemm_launch): 1x1 stream (one tap
+    # only), heads, ping-pong (Co % 256 or % 192 == 0 and ceil(M / 256) * (Co / bn) >= 256 tiles), layer1 row ring
+    # (64 -> 64, 3x3 s1, rows of 64 / 128 / 256), LDS-DMA ring (Co > 64 and ceil(M / 256) * ceil(Co / 128) >= 256),
+    # else the register-staged tiled kernel
+    ("conv", (2, 64, 16, 16, 128, 3, 2, 1)),      # M = 128: 1 tile, the generic tiled kernel (128 x 128)
+    ("conv", (3, 64, 41, 37, 192, 3, 2, 1)),      # M = 1197: 5 x 2 ring tiles < 256, so the tiled kernel, ragged M and Co
+    ("conv", (8, 64, 128, 128, 64, 3, 1, 1)),     # layer1 persistent kernel: 512 tiles, 2 per workgroup on 256 CUs (the
+                                                  # running fp32 sums cross tiles)
+    ("conv", (10, 64, 100, 64, 192, 3, 1, 1)),    # M = 64000: 250 ping-pong tiles (bn 192) < 256, 250 x 2 ring tiles: the
+                                                  # ring kernel, last tile row ragged
+    ("conv", (13, 64, 60, 48, 384, 3, 1, 1)),     # M = 37440: 147 x 2 ping-pong tiles (bn 192), ragged last tile
+    ("stem", (1, 260, 256)),                      # the direct stem conv (7x7 s2, one input channel)
+]
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16], ids=["bfloat16", "float16"])
+@pytest.mark.parametrize("kind,case", EXACT_STAT_CASES, ids=["tiled", "tiled-ragged", "layer1", "ring", "pingpong", "stem"])
+def test_conv_forward_statistics_exact(kind, case, dtype):
+    """x in {-1, 0, 1} and four taps of +-1 per output channel: every accumulator is an integer in [-4, 4], so y, the
+    per-channel sum of y and the sum of y^2 from the epilogue must equal the float64 convolution exactly -- one pixel or one
+    wave's partial lost from either sum fails, whatever the tensor's size."""
+    from scdhip import ops
+    if kind == "stem":
+        (N, H, W), Cin, Cout, k, s, p = case, 1, 64, 7, 2, 3
+    else:
+        N, Cin, H, W, Cout, k, s, p = case
+    g = torch.Generator(device=DEV).manual_seed(Cout + H)
+    x = torch.randint(-1, 2, (N, Cin, H, W), device=DEV, generator=g).float()
+    idx = torch.rand(Cout, Cin * k * k, device=DEV, generator=g).topk(4, dim=1).indices
+    sign = (torch.randint(0, 2, (Cout, 4), device=DEV, generator=g) * 2 - 1).float()
+    w = torch.zeros(Cout, Cin * k * k, device=DEV).scatter_(1, idx, sign).view(Cout, Cin, k, k)
+    ref = _four_tap_conv(x.double(), idx, sign.double(), k, s, p)
+    if N * H * W * Cout <= 1 << 16:       # anchor the gather reference itself on torch's float64 convolution
+        assert torch.equal(ref.cpu(), F.conv2d(x.double().cpu(), w.double().cpu(), stride=s, padding=p))
+    assert ref.abs().max().item() <= 4 and (ref != 0).any()
+    stats = ops.new_stats(Cout, DEV)
+    if kind == "stem":
+        assert ops.stem_direct_ok(x, dtype)
+        y = ops.stem_conv_fwd(x, ops.pack_weight(w, dtype, 0, ldp=64), stats=stats)
+    else:
+        y = ops.conv_fwd(nhwc(x, dtype), ops.pack_weight(w, dtype, 0), Cout, k, k, s, p, stats=stats)
+    torch.cuda.synchronize()
+    assert torch.equal(y.permute(0, 3, 1, 2).double(), ref)
+    st = stats.view(-1, 2, Cout).sum(0)
+    assert torch.equal(st[0], ref.sum((0, 2, 3))), (st[0] - ref.sum((0, 2, 3))).abs().max().item()
+    assert torch.equal(st[1], (ref * ref).sum((0, 2, 3))), (st[1] - (ref * ref).sum((0, 2, 3))).abs().max().item()
 
 
 # shapes large enough (>= 256 tiles of 256 pixels) for the bf16 ping-pong kernels: halo variant (3x3 s1,
@@ -324,7 +417,8 @@ def test_stem_im2col_gemm_pool(dtype):
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("shape", [(2, 512, 512), (1, 260, 256)])
 def test_stem_direct_bf16(shape, dtype):
-    """Direct stem conv (tap tile built in LDS) forward + BN sums and its weight gradient vs torch fp32."""
+    """Direct stem conv (tap tile built in LDS) forward + BN sums and its weight gradient vs torch fp32.  The sum of
+    y^2 is held to SQ_TOL (observed here: 2.5e-9 to 9.1e-9; see assert_sum_squares)."""
     from scdhip import ops
     N, H, W = shape
     g = torch.Generator().manual_seed(5)
@@ -343,6 +437,7 @@ def test_stem_direct_bf16(shape, dtype):
     st = stats.view(-1, 2, 64).sum(0).cpu()
     yd = yr.detach().double()
     np.testing.assert_allclose(st[0].numpy(), yd.sum((0, 2, 3)).numpy(), rtol=1e-3, atol=1e-2 * yd.numel() ** 0.5)
+    assert_sum_squares(st[1], yd, dtype, "stem %s" % (shape,))
     dw = torch.full((64, 1, 7, 7), 0.25, device=DEV)
     ops.stem_conv_wgrad(nhwc(dy, dtype), xd, dw, accumulate=True)
     assert rel_err(dw - 0.25, wr.grad) < TOL[dtype] * 3
