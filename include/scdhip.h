@@ -377,6 +377,28 @@ int scd_render_center_targets(const float* locs, const int* counts, int B, int K
 size_t scd_augment_workspace(int B);
 int scd_augment_tiles(const float* in, float* out, int B, int H, int W, const uint8_t* flips, const float* jitter,
                       const float* noise, float noise_sv, unsigned long long seed, void* workspace, void* stream);
+/* The same from a device-resident store of nstore tiles (H,W): out[b] is what scd_augment_tiles gives for
+ * in[b] = store[ids[b]], bit for bit; both passes read the tile in place at the 64-bit offset (long)ids[b]*H*W, nothing
+ * is gathered.  ids (B) int32 on the device, repeats allowed, NOT range-checked by the kernel: the caller guarantees
+ * 0 <= ids[b] < nstore.  SCD_ERR_ARG and no launch for a NULL store / ids / out, nstore < 1, store == out and
+ * scd_augment_tiles' B / H / W rules.  scd_augment_tiles is these kernels with identity indexing. */
+int scd_augment_tiles_indexed(const float* store, long nstore, const int* ids, float* out, int B, int H, int W,
+                              const uint8_t* flips, const float* jitter, const float* noise, float noise_sv,
+                              unsigned long long seed, void* workspace, void* stream);
+/* The label half of a training batch from a device-resident archive: SCD.flipLocs, SCD.rotateLocs and _pack_locs of
+ * trainer/dataset/scdx16p100.py per tile, one workgroup each.  rows (T,8) fp32 and offsets (N+1) int64 hold the
+ * archive's labels as CSR (tile i owns rows[offsets[i]:offsets[i+1]]); ids (B) int32 (not range-checked); flips (B,2)
+ * u8, nullable; cs (B,2) fp32 = (cos, sin) of -angle*pi/180 computed in fp64 and rounded, nullable = no rotation.
+ * Without cs the tile's flipped rows; with cs every flipped row's nine replicas (row outermost, k = 3 kx + ky innermost;
+ * x: c, 2 size - 1 - c, -1 - c; y: c, -1 - c, 2 size - 1 - c) turned about (size / 2 - 0.5, size / 2 - 0.5) in fp32 in
+ * the host's operation order (every multiply, add, subtract, divide and sqrt correctly rounded, none contracted: the
+ * bits of the same formulas in numpy float32; flips too use `size`, SCD.flipLocs' 128; a centre on the rotation centre stays, a zero offset
+ * stays zero, a zero major axis gives NaN), kept when the centre truncated toward zero lies in [0, size) on both axes.
+ * locs (B,K,8): the first K kept rows in candidate order, zero beyond; counts (B) int32 = min(kept, K); trunc != 0
+ * truncates columns 0 and 1 toward zero.  SCD_ERR_ARG and no launch for a NULL rows / offsets / ids / locs / counts,
+ * B < 1, size < 1, K < 1 or K > 64. */
+int scd_pack_locs(const float* rows, const long* offsets, const int* ids, int B, const uint8_t* flips, const float* cs,
+                  int size, int K, int trunc, float* locs, int* counts, void* stream);
 /* Random-angle rotation of a training batch (the step datasets/scds/scdx16p100.py:443-451 holds switched off):
  * out[b] = argumentations.rotate(in[b], angle_b, MirrorPadding, Bilinear) (datasets/argumentations.py:148-159) for
  * in, out (B,H,W) fp32 and cs (B,2) fp64 on the device = (cos, sin) of each tile's angle in radians: torch-'reflect'

@@ -2,12 +2,15 @@
 
 Same default keys and the same overlay rule: a JSON config replaces only keys that already
 exist (configuration.py:150-153); string values may reference other keys as `{key}` format
-fields.  Three keys are added: ``computeDtype`` ("bf16" | "fp16" | "fp32"), the MFMA precision of the
+fields.  Four keys are added: ``computeDtype`` ("bf16" | "fp16" | "fp32"), the MFMA precision of the
 HIP path (the reference trains in fp32 without AMP), ``stepGraph`` (true | false, default false):
 replay the training step as a captured HIP graph after two eager steps (single-process runs;
-scdhip/graph.py -- measured slower than eager issue on ROCm 7), and ``rotateAugmentation``
+scdhip/graph.py -- measured slower than eager issue on ROCm 7), ``rotateAugmentation``
 (degrees, default 0.0 = off): the `.d` dataset plugins rotate every training tile and its labels by an angle
-drawn uniformly from [-value, value] (the reference holds this step switched off).
+drawn uniformly from [-value, value] (the reference holds this step switched off), and
+``residentDataset`` (true | false, default false): the `.d` dataset plugins upload the whole archive (tiles and
+labels) to the device at the first training batch and build every batch there from the host's random draws
+(it raises when the archive does not fit into the device's free memory).
 """
 import os
 
@@ -46,6 +49,7 @@ class Configuration:
         c["computeDtype"] = "bf16"
         c["stepGraph"] = False
         c["rotateAugmentation"] = 0.0
+        c["residentDataset"] = False
         self.config = c
 
     # -- formatted / plain accessors (configuration.py:46-146)
@@ -85,6 +89,7 @@ class Configuration:
     computeDtype = property(lambda s: s.config["computeDtype"])
     stepGraph = property(lambda s: bool(s.config["stepGraph"]))
     rotateAugmentation = property(lambda s: float(s.config["rotateAugmentation"]))
+    residentDataset = property(lambda s: bool(s.config["residentDataset"]))
 
     def useGPU(self):
         # a bound method, hence always truthy when tested without a call (reference quirk)

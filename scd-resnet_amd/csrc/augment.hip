@@ -13,6 +13,7 @@
 // Per-pixel noise comes from the caller (a device tensor: parity tests replay the reference's draws) or from
 // a counter-based generator (splitmix64 of (seed, tile, pixel) -> Box-Muller), so the batch path needs no
 // host random numbers.
+// scd_augment_tiles_indexed runs the same two kernels on tiles ids[b] of a device-resident store, read in place.
 //
 // scd_rotate_tiles: the per-sample random rotation the reference wrote as the last step of SCD.argumentation and left
 // switched off (scdx16p100.py:443-451): out[b] = argumentations.rotate(in[b], angle_b, MirrorPadding, Bilinear)
@@ -28,13 +29,21 @@ namespace {
 constexpr int AUG_SLICES = 64;
 constexpr int AUG_THREADS = 256;
 
-__global__ __launch_bounds__(AUG_THREADS) void aug_stats_kernel(const float* __restrict__ in, long hw,
+// Tile b of a batch is tile ids[b] of `in` (scd_augment_tiles_indexed: a gather from a device-resident store, read in
+// place by both passes) or, with ids NULL, tile b itself (scd_augment_tiles).  The offset is 64-bit: the canonical
+// store holds 1.3e10 elements.
+__device__ __forceinline__ const float* aug_tile(const float* in, const int* ids, int b, long hw) {
+    return in + (long)(ids ? ids[b] : b) * hw;
+}
+
+__global__ __launch_bounds__(AUG_THREADS) void aug_stats_kernel(const float* __restrict__ in,
+                                                                const int* __restrict__ ids, long hw,
                                                                 double* __restrict__ part) {
     const int b = blockIdx.y, s = blockIdx.x, tid = threadIdx.x;
     const long n4 = hw >> 2;
     const long per = (n4 + AUG_SLICES - 1) / AUG_SLICES;
     const long beg = s * per, end = min(n4, beg + per);
-    const float4* p = (const float4*)(in + (long)b * hw);
+    const float4* p = (const float4*)aug_tile(in, ids, b, hw);
     double s1 = 0.0, s2 = 0.0;
     for (long i = beg + tid; i < end; i += AUG_THREADS) {
         float4 v = p[i];
@@ -74,6 +83,7 @@ __device__ __forceinline__ float2 gauss2(unsigned long long seed, unsigned long 
 
 struct AugArgs {
     const float* in;
+    const int* ids;          // (B) tile of `in` per batch slot, nullable = identity
     float* out;
     const double* part;
     const uint8_t* flips;    // (B,2): [flip x (dim 2), flip y (dim 1)]
@@ -105,7 +115,7 @@ __global__ __launch_bounds__(AUG_THREADS) void aug_apply_kernel(AugArgs a) {
     const bool fx = a.flips && a.flips[b * 2], fy = a.flips && a.flips[b * 2 + 1];
     const int w4 = a.W >> 2;
     const long n4 = hw >> 2;
-    const float* src = a.in + (long)b * hw;
+    const float* src = aug_tile(a.in, a.ids, b, hw);
     float* dst = a.out + (long)b * hw;
     for (long i = (long)blockIdx.x * AUG_THREADS + tid; i < n4; i += (long)gridDim.x * AUG_THREADS) {
         int y = (int)(i / w4), x4 = (int)(i - (long)y * w4);
@@ -214,20 +224,34 @@ int rotate_tiles_launch(RotTiles a, hipStream_t st) {
 
 extern "C" size_t scd_augment_workspace(int B) { return (size_t)B * AUG_SLICES * 2 * sizeof(double); }
 
-extern "C" int scd_augment_tiles(const float* in, float* out, int B, int H, int W, const uint8_t* flips,
-                                 const float* jitter, const float* noise, float noise_sv, unsigned long long seed,
-                                 void* workspace, void* stream) {
+// the two launches of both entry points: ids NULL = identity indexing
+static int augment_launch(const float* in, const int* ids, float* out, int B, int H, int W, const uint8_t* flips,
+                          const float* jitter, const float* noise, float noise_sv, unsigned long long seed,
+                          void* workspace, void* stream) {
     if (B < 1 || H < 1 || W < 4 || (W & 3) || (long)H * W >= (1L << 31) || in == out) return SCD_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
     const long hw = (long)H * W;
     double* part = (double*)workspace;
-    hipLaunchKernelGGL(aug_stats_kernel, dim3(AUG_SLICES, B), dim3(AUG_THREADS), 0, st, in, hw, part);
+    hipLaunchKernelGGL(aug_stats_kernel, dim3(AUG_SLICES, B), dim3(AUG_THREADS), 0, st, in, ids, hw, part);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
-    AugArgs a{in, out, part, flips, jitter, noise, noise_sv, seed, H, W};
+    AugArgs a{in, ids, out, part, flips, jitter, noise, noise_sv, seed, H, W};
     int bx = (int)min(64L, (hw / 4 + AUG_THREADS - 1) / AUG_THREADS);
     hipLaunchKernelGGL(aug_apply_kernel, dim3(bx, B), dim3(AUG_THREADS), 0, st, a);
     SCD_RETURN_LAUNCH();
+}
+
+extern "C" int scd_augment_tiles(const float* in, float* out, int B, int H, int W, const uint8_t* flips,
+                                 const float* jitter, const float* noise, float noise_sv, unsigned long long seed,
+                                 void* workspace, void* stream) {
+    return augment_launch(in, nullptr, out, B, H, W, flips, jitter, noise, noise_sv, seed, workspace, stream);
+}
+
+extern "C" int scd_augment_tiles_indexed(const float* store, long nstore, const int* ids, float* out, int B, int H,
+                                         int W, const uint8_t* flips, const float* jitter, const float* noise,
+                                         float noise_sv, unsigned long long seed, void* workspace, void* stream) {
+    if (!store || !ids || !out || nstore < 1) return SCD_ERR_ARG;
+    return augment_launch(store, ids, out, B, H, W, flips, jitter, noise, noise_sv, seed, workspace, stream);
 }
 
 extern "C" int scd_rotate_tiles_mapped(const float* in, float* out, int B, int H, int W, const double* cs, int mapping,

@@ -88,7 +88,114 @@ __global__ __launch_bounds__(256) void render_center_kernel(const float* __restr
     }
 }
 
+// ---- scd_pack_locs: the label half of a training batch built from a device-resident archive -------------------------
+// What SCD.gpu_batch does per tile on the host (trainer/dataset/scdx16p100.py: flipLocs, rotateLocs, _pack_locs), one
+// workgroup per tile: the tile's CSR rows, flipped, with a rotation each row's nine replicas turned in float32 in the
+// host's operation order (datasets/preprocessor/scdManual.py _turn / rotateCoordinates) and filtered by the truncated
+// centre, compacted in candidate order into the first K slots.
+
+constexpr int PACK_THREADS = 256;
+
+// _turn: (x, y) turned through its length m and direction (x / m, y / m); a zero vector gives NaN.  Every operation
+// rounds once, as numpy's float32 does: plain operators written in this file, so the `fp contract(off)` above holds
+// for them (the __f*_rn helpers are header functions the pragma does not reach, and __fsqrt_rn is the 1-ulp hardware
+// sqrt), and sqrtf / the division, which hipcc rounds correctly by default.
+__device__ __forceinline__ void pack_turn(float x, float y, float ca, float sa, float& ox, float& oy, float& m) {
+    m = sqrtf(x * x + y * y);
+    const float s = y / m, c = x / m;
+    ox = m * (c * ca - s * sa);
+    oy = m * (s * ca + c * sa);
+}
+
+__global__ __launch_bounds__(PACK_THREADS) void pack_locs_kernel(const float* __restrict__ rows,
+                                                                 const long* __restrict__ offsets,
+                                                                 const int* __restrict__ ids,
+                                                                 const uint8_t* __restrict__ flips,
+                                                                 const float* __restrict__ cs, int size, int K, int trunc,
+                                                                 float* __restrict__ locs, int* __restrict__ counts) {
+    __shared__ int wtot[PACK_THREADS / 64];
+    __shared__ int base_s;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const long r0 = offsets[ids[b]];
+    const long n = offsets[ids[b] + 1] - r0;
+    const bool rot = cs != nullptr;
+    const long ncand = rot ? 9 * n : n;
+    const bool fx = flips && flips[b * 2], fy = flips && flips[b * 2 + 1];
+    const float ca = rot ? cs[b * 2] : 1.f, sa = rot ? cs[b * 2 + 1] : 0.f;
+    const float edge = (float)(size - 1), far = (float)(2 * size - 1), fsize = (float)size;
+    const float shift = (float)(0.5 - (double)(size / 2));
+    float* out = locs + (long)b * K * 8;
+    if (tid == 0) base_s = 0;
+    __syncthreads();
+    for (long c0 = 0; c0 < ncand && base_s < K; c0 += PACK_THREADS) {
+        const long c = c0 + tid;
+        bool keep = false;
+        float v[8];
+        if (c < ncand) {
+            const long row = rot ? c / 9 : c;
+            const int k = rot ? (int)(c - row * 9) : 0;
+            const float4 lo = *(const float4*)(rows + (r0 + row) * 8), hi = *(const float4*)(rows + (r0 + row) * 8 + 4);
+            v[0] = lo.x; v[1] = lo.y; v[2] = lo.z; v[3] = lo.w;
+            v[4] = hi.x; v[5] = hi.y; v[6] = hi.z; v[7] = hi.w;
+            if (fx) { v[0] = edge - v[0]; v[2] = -v[2]; v[4] = -v[4]; }       // flipLocs
+            if (fy) { v[1] = edge - v[1]; v[3] = -v[3]; v[5] = -v[5]; }
+            keep = true;
+            if (rot) {
+                const int kx = k / 3, ky = k - kx * 3;                                  // rotateLocs' replica k
+                if (kx) { v[0] = kx == 1 ? far - v[0] : -1.f - v[0]; v[2] = -v[2]; v[4] = -v[4]; }
+                if (ky) { v[1] = ky == 1 ? -1.f - v[1] : far - v[1]; v[3] = -v[3]; v[5] = -v[5]; }
+                const float sx = v[0] + shift, sy = v[1] + shift;   // rotateCoordinates
+                if (!(sx == 0.f && sy == 0.f)) {          // a centre on the rotation centre stays where it is
+                    float tx, ty, m;
+                    pack_turn(sx, sy, ca, sa, tx, ty, m);
+                    v[0] = tx - shift;
+                    v[1] = ty - shift;
+                }
+                float ox, oy, len;
+                pack_turn(v[2], v[3], ca, sa, ox, oy, len);
+                v[2] = len == 0.f ? 0.f : ox;                                           // a zero offset stays zero
+                v[3] = len == 0.f ? 0.f : oy;
+                pack_turn(v[4], v[5], ca, sa, ox, oy, len);                             // a zero major axis: NaN
+                v[4] = ox; v[5] = oy;
+                const float cx = truncf(v[0]), cy = truncf(v[1]);                       // NaN compares false: dropped
+                keep = cx >= 0.f && cx < fsize && cy >= 0.f && cy < fsize;
+            }
+        }
+        const unsigned long long bal = __ballot(keep);
+        const int rank = __popcll(bal & ((1ull << lane) - 1ull));
+        if (lane == 0) wtot[wv] = __popcll(bal);
+        __syncthreads();
+        if (keep) {
+            int off = base_s + rank;
+            for (int w = 0; w < wv; ++w) off += wtot[w];
+            if (off < K) {
+                if (trunc) { v[0] = truncf(v[0]); v[1] = truncf(v[1]); }
+                *(float4*)(out + off * 8) = make_float4(v[0], v[1], v[2], v[3]);
+                *(float4*)(out + off * 8 + 4) = make_float4(v[4], v[5], v[6], v[7]);
+            }
+        }
+        __syncthreads();
+        if (tid == 0) {
+            int s = 0;
+            for (int w = 0; w < PACK_THREADS / 64; ++w) s += wtot[w];
+            base_s += s;
+        }
+        __syncthreads();
+    }
+    const int cnt = min(base_s, K);
+    if (tid == 0) counts[b] = cnt;
+    for (int i = cnt * 8 + tid; i < K * 8; i += PACK_THREADS) out[i] = 0.f;
+}
+
 }  // namespace
+
+extern "C" int scd_pack_locs(const float* rows, const long* offsets, const int* ids, int B, const uint8_t* flips,
+                             const float* cs, int size, int K, int trunc, float* locs, int* counts, void* stream) {
+    if (!rows || !offsets || !ids || !locs || !counts || B < 1 || size < 1 || K < 1 || K > MAXOBJ) return SCD_ERR_ARG;
+    hipLaunchKernelGGL(pack_locs_kernel, dim3(B), dim3(PACK_THREADS), 0, (hipStream_t)stream, rows, offsets, ids, flips,
+                       cs, size, K, trunc, locs, counts);
+    SCD_RETURN_LAUNCH();
+}
 
 extern "C" int scd_render_center_targets(const float* locs, const int* counts, int B, int K, int H, float threshold,
                                          float* heat, uint8_t* mask, float* regr, int64_t* inds, void* stream) {

@@ -119,6 +119,8 @@ SIGNATURES = {
     "scd_decode_topk": (I, [P, I, I, I, I, P, I, P, I, P, P, P, P, P, P, P, P]),
     "scd_augment_workspace": (c_size_t, [I]),
     "scd_augment_tiles": (I, [P, P, I, I, I, P, P, P, F, ctypes.c_ulonglong, P, P]),
+    "scd_augment_tiles_indexed": (I, [P, L, P, P, I, I, I, P, P, P, F, ctypes.c_ulonglong, P, P]),
+    "scd_pack_locs": (I, [P, P, P, I, P, P, I, I, I, P, P, P]),
     "scd_rotate_tiles": (I, [P, P, I, I, I, P, P]),
     "scd_rotate_tiles_mapped": (I, [P, P, I, I, I, P, I, P]),
     "scd_slide_workspace": (c_size_t, [I]),

@@ -1570,10 +1570,98 @@ def augment_tiles(tiles, flips=None, jitter=None, noise=None, noise_sv=0.0, seed
     return out.view(shape)
 
 
+def _device_ids(ids, n, dev, what):
+    """ids as a device int32 tensor: a host sequence is range-checked against [0, n) and uploaded (IndexError before
+    any launch), a device int tensor is taken as it is (checking it would synchronise)."""
+    if torch.is_tensor(ids):
+        _need_gpu(ids)
+        if ids.dtype not in (torch.int32, torch.int64) or ids.dim() != 1:
+            raise RuntimeError("%s: ids must be a one-dimensional int32 / int64 tensor" % what)
+        return ids.to(torch.int32).contiguous()
+    ids = [int(i) for i in ids]
+    for i in ids:
+        if not 0 <= i < n:
+            raise IndexError("%s: id %d outside the store's %d tiles" % (what, i, n))
+    return torch.tensor(ids, dtype=torch.int32).to(dev)
+
+
+def augment_tiles_indexed(store, ids, flips=None, jitter=None, noise=None, noise_sv=0.0, seed=0, out=None):
+    """augment_tiles(store[ids], ...) without the gather (scd_augment_tiles_indexed): both kernel passes read tile
+    ids[b] in place from the device-resident `store` (N,H,W) or (N,1,H,W) fp32, contiguous.  ids: a host sequence
+    (checked against [0, N): IndexError) or a device int tensor (not checked); repeats allowed.  Returns (B,1,H,W),
+    bit for bit what augment_tiles gives for the stacked tiles."""
+    _need_gpu(store, flips, jitter, noise, out)
+    if store.dtype != torch.float32 or not store.is_contiguous():
+        raise RuntimeError("augment_tiles_indexed: a contiguous fp32 store expected, got %s" % store.dtype)
+    if store.dim() not in (3, 4) or (store.dim() == 4 and store.shape[1] != 1):
+        raise RuntimeError("augment_tiles_indexed: (N,H,W) or (N,1,H,W) expected, one channel per tile")
+    N, H, W = store.shape[0], store.shape[-2], store.shape[-1]
+    i = _device_ids(ids, N, store.device, "augment_tiles_indexed")
+    B = i.numel()
+    if out is None:
+        out = torch.empty(B, 1, H, W, device=store.device)
+    elif out.dtype != torch.float32 or out.numel() != B * H * W or not out.is_contiguous():
+        raise RuntimeError("augment_tiles_indexed: out must be a contiguous fp32 tensor of B tiles")
+    f = flips.to(torch.uint8).contiguous() if flips is not None else None
+    j = jitter.float().contiguous() if jitter is not None else None
+    n = noise.float().contiguous() if noise is not None else None
+    ws = torch.empty(L.lib().scd_augment_workspace(B), dtype=torch.uint8, device=store.device)
+    L.call("scd_augment_tiles_indexed", ptr(store), N, ptr(i), ptr(out), B, H, W, ptr(f), ptr(j), ptr(n),
+           float(noise_sv), int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(ws), stream())
+    return out.view(B, 1, H, W)
+
+
+def pack_locs_cs(angles_deg):
+    """(B,2) float32 host tensor of (cos, sin) of rotateCoordinates' turn = -angle * pi / 180: taken in float64 and
+    rounded to float32, which is what a float32 torch tensor times the Python float multiplies by."""
+    turns = [-float(a) * math.pi / 180 for a in angles_deg]
+    return torch.tensor([[math.cos(t), math.sin(t)] for t in turns], dtype=torch.float64).reshape(-1, 2).float()
+
+
+def pack_locs(rows, offsets, ids, flips=None, angles_deg=None, size=128, K=30, trunc=True, cs=None):
+    """A batch's label rows from a device-resident archive (scd_pack_locs): SCD.flipLocs, SCD.rotateLocs (when
+    angles_deg is given) and _pack_locs of trainer/dataset/scdx16p100.py per tile.  rows (T,8) fp32 and offsets (N+1)
+    int64 on the device are the archive's labels as CSR; ids a host sequence (checked: IndexError) or a device int
+    tensor; flips (B,2) bool/u8 on the device; angles_deg B host numbers, or cs = pack_locs_cs(angles) already on the
+    device.  `size` is the map's side for the flip (size - 1 - c) as for the rotation; SCD.flipLocs always flips about
+    HEATMAPSIZE = 128, so the two agree at size 128 only.  Returns (locs (B,K,8) fp32, counts (B,) int32) on the
+    device."""
+    _need_gpu(rows, offsets, flips, cs)
+    if rows.dtype != torch.float32 or rows.dim() != 2 or rows.shape[1] != 8 or not rows.is_contiguous():
+        raise RuntimeError("pack_locs: rows must be a contiguous (T,8) fp32 tensor")
+    if offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.numel() < 2 or not offsets.is_contiguous():
+        raise RuntimeError("pack_locs: offsets must be a contiguous (N+1,) int64 tensor")
+    dev = rows.device
+    i = _device_ids(ids, offsets.numel() - 1, dev, "pack_locs")
+    B = i.numel()
+    if angles_deg is not None:
+        if cs is not None:
+            raise RuntimeError("pack_locs: angles_deg or cs, not both")
+        cs = pack_locs_cs(angles_deg).to(dev)
+    if cs is not None and (cs.dtype != torch.float32 or tuple(cs.shape) != (B, 2) or not cs.is_contiguous()):
+        raise RuntimeError("pack_locs: %d angles for %d tiles" % (cs.numel() // 2, B))
+    f = flips.to(torch.uint8).contiguous() if flips is not None else None
+    if f is not None and f.numel() != 2 * B:
+        raise RuntimeError("pack_locs: flips must be (B,2)")
+    if rows.shape[0] == 0:          # an archive without a single object: no row is read, but the pointer must exist
+        rows = torch.zeros(1, 8, device=dev)
+    locs = torch.empty(B, K, 8, device=dev)
+    counts = torch.empty(B, dtype=torch.int32, device=dev)
+    L.call("scd_pack_locs", ptr(rows), ptr(offsets), ptr(i), B, ptr(f), ptr(cs), int(size), int(K), int(bool(trunc)),
+           ptr(locs), ptr(counts), stream())
+    return locs, counts
+
+
 ROTATE_MAPS = {"row": 0, "64x4": 1, "32x8": 2, "16x16": 3}      # SCD_ROTATE_MAP_*: a wave's pixels x rows
 
 
-def rotate_tiles(tiles, angles_deg, out=None, mapping=None):
+def rotate_tiles_cs(angles_deg):
+    """(B,2) float64 host tensor of (cos, sin) of angle * pi / 180, rotate_tiles' per-tile coefficients."""
+    ang = [float(a) * math.pi / 180.0 for a in angles_deg]
+    return torch.tensor([[math.cos(a), math.sin(a)] for a in ang], dtype=torch.float64).reshape(-1, 2)
+
+
+def rotate_tiles(tiles, angles_deg, out=None, mapping=None, cs=None):
     """The random-angle rotation of a training batch on the GPU (scd_rotate_tiles; the step scdx16p100.py:443-451
     holds switched off): out[b] = argumentations.rotate(tiles[b], angles_deg[b], MirrorPadding, Bilinear)
     (argumentations.py:148-159), positive angles counter-clockwise as torchvision's.  tiles (B,1,H,W) or (B,H,W)
@@ -1581,7 +1669,8 @@ def rotate_tiles(tiles, angles_deg, out=None, mapping=None):
     the expression slide_rotate_clips' library side uses (angle * pi / 180).  The rotation is torchvision's tensor
     rotate restated, as in slide_rotate_clips: equality with real torchvision has not been measured.  Returns a new
     tensor, or `out` (fp32, contiguous, not `tiles`) viewed in the tiles' shape.  mapping: a ROTATE_MAPS key, for
-    tools/rotate_bench.py; every mapping gives the same bits."""
+    tools/rotate_bench.py; every mapping gives the same bits.  cs: rotate_tiles_cs(angles) already on the device (a
+    caller that uploads its per-batch values in one copy); angles_deg is then not read."""
     _need_gpu(tiles, out)
     if tiles.dtype != torch.float32:
         raise RuntimeError("rotate_tiles: fp32 tiles expected, got %s" % tiles.dtype)
@@ -1590,14 +1679,17 @@ def rotate_tiles(tiles, angles_deg, out=None, mapping=None):
         raise RuntimeError("rotate_tiles: (B,H,W) or (B,1,H,W) expected, one channel per tile")
     t = tiles.contiguous()
     B, H, W = shape[0], shape[-2], shape[-1]
-    ang = [float(a) * math.pi / 180.0 for a in angles_deg]
-    if len(ang) != B:
-        raise RuntimeError("rotate_tiles: %d angles for %d tiles" % (len(ang), B))
+    host = rotate_tiles_cs(angles_deg) if cs is None else None
+    if host is not None and host.shape[0] != B:
+        raise RuntimeError("rotate_tiles: %d angles for %d tiles" % (host.shape[0], B))
     if out is None:
         out = torch.empty_like(t)
     elif out.dtype != torch.float32 or out.numel() != t.numel() or not out.is_contiguous():
         raise RuntimeError("rotate_tiles: out must be a contiguous fp32 tensor of the tiles' size")
-    cs = torch.tensor([[math.cos(a), math.sin(a)] for a in ang], dtype=torch.float64).reshape(-1, 2).to(t.device)
+    if host is not None:
+        cs = host.to(t.device)
+    elif not cs.is_cuda or cs.dtype != torch.float64 or tuple(cs.shape) != (B, 2) or not cs.is_contiguous():
+        raise RuntimeError("rotate_tiles: cs must be a contiguous (B,2) float64 tensor on the device")
     if mapping is None:
         L.call("scd_rotate_tiles", ptr(t), ptr(out), B, H, W, ptr(cs), stream())
     else:

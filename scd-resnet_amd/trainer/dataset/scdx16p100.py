@@ -31,6 +31,11 @@ positions it holds.  The reference's CUDA path pins cuda:0 (:316-356); here the 
 The random-angle rotation the reference wrote as the augmentation's last step and left switched off (:443-486) runs
 here when the configuration key rotateAugmentation (maximum absolute angle, degrees) is above 0: scd_rotate_tiles
 on the augmented tiles, SCD.rotateLocs on the flipped labels; the validation set is never rotated.
+With the configuration key residentDataset on, the first gpu_batch uploads the whole archive to the device (tiles as
+one store, labels as CSR) and every batch is built there from the same host draws: scd_augment_tiles_indexed,
+scd_rotate_tiles, scd_pack_locs (the flips, the rotation and the packing of the labels in one launch) and
+scd_render_center_targets, without reading a host tile or label.  With the key off, the default,
+nothing of this runs.
 """
 import io
 import json
@@ -292,8 +297,11 @@ class SCD(Dataset):
         scd_render_center_targets): {"xs": [(B,1,S,S)], "ys": [heat, mask, regr, inds]} on the device, the
         reference's __getitem__ stacked over `indices` (positions in the shuffled order).  With the configuration's
         rotateAugmentation > 0, scd_rotate_tiles and rotateLocs follow the augmentation and the flips."""
+        from configuration import defaultConfig
         from scdhip import ops
         dev = device or self.device
+        if defaultConfig.residentDataset:
+            return self._resident_batch(indices, dev)
         if 0 in indices:
             shuffle(self.order)      # the reference reshuffles when index 0 is fetched (scdx16p100.py:302-305)
         ids = [self.order[i] for i in indices]
@@ -309,6 +317,79 @@ class SCD(Dataset):
         l, n = _pack_locs(rows, trunc=True)
         ys = ops.render_center_targets(torch.from_numpy(l).to(dev), torch.from_numpy(n).to(dev), HEATMAPSIZE,
                                        THRESHOLDIOU)
+        return {"xs": [xs], "ys": ys}
+
+    # ------------------------------------------------------------------ device-resident archive
+    def _buildResident(self, dev, chunk=256):
+        """The whole archive on `dev`: the tiles as one (N,H,W) fp32 store in archive order, uploaded `chunk` tiles at
+        a time, and the labels as CSR (rows (T,8) fp32, offsets (N+1) int64).  Raises when the tiles have more than
+        one shape or when the bytes needed exceed the device's free memory; nothing is allocated then."""
+        N = len(self.samples)
+        shapes = {tuple(s.shape[-2:]) for s in self.samples}
+        if N == 0 or len(shapes) != 1:
+            raise RuntimeError("scdx16p100: residentDataset needs an archive of tiles of one shape, got %s" % (
+                sorted(shapes) or "no tile"))
+        H, W = shapes.pop()
+        lens = [int(len(b)) for b in self.bounds]
+        T = sum(lens)
+        need = N * H * W * 4 + T * 8 * 4 + (N + 1) * 8
+        free = int(torch.cuda.mem_get_info(dev)[0])
+        if need > free:
+            raise RuntimeError("scdx16p100: residentDataset needs %d bytes on %s for %d tiles of %d x %d and %d label "
+                               "rows, %d bytes are free" % (need, dev, N, H, W, T, free))
+        store = torch.empty(N, H, W, dtype=torch.float32, device=dev)
+        for c0 in range(0, N, chunk):
+            part = torch.stack(self.samples[c0:c0 + chunk]).reshape(-1, H, W)
+            store[c0:c0 + len(part)].copy_(part)
+        rows = torch.cat([b.reshape(-1, 8).float() for b in self.bounds]) if T else torch.zeros(0, 8)
+        offsets = torch.zeros(N + 1, dtype=torch.int64)
+        offsets[1:] = torch.tensor(lens, dtype=torch.int64).cumsum(0)
+        self.resident = {"device": dev, "store": store, "rows": rows.to(dev), "offsets": offsets.to(dev)}
+        _log("Resident Dataset: {} Tiles of {} x {} and {} Label Rows, {:.3f} GiB on {}".format(
+            N, H, W, T, need / 2.0 ** 30, dev))
+
+    def _resident_batch(self, indices, dev):
+        """gpu_batch from the device-resident archive: the same draws in the same order, one upload of the batch's
+        ids, flips, jitter factors and rotation coefficients, then scd_augment_tiles_indexed, scd_rotate_tiles (when
+        rotateAugmentation > 0), scd_pack_locs and scd_render_center_targets.  No host tile or label is read and
+        there is no explicit synchronise (the one upload, from pageable memory, is a blocking copy on the current
+        stream, as every upload of the host path is)."""
+        from scdhip import ops
+        dev = torch.device(dev)
+        if dev.type == "cuda" and dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        res = getattr(self, "resident", None)
+        if res is None:
+            self._buildResident(dev)
+            res = self.resident
+        elif res["device"] != dev:
+            raise RuntimeError("scdx16p100: the resident archive lives on %s, a batch for %s was asked for" % (
+                res["device"], dev))
+        if 0 in indices:
+            shuffle(self.order)      # as gpu_batch
+        ids = [self.order[i] for i in indices]
+        B = len(ids)
+        N = res["store"].shape[0]
+        if B and not (0 <= min(ids) and max(ids) < N):
+            raise IndexError("scdx16p100: tile id outside the resident archive's %d tiles" % N)
+        flips, jit, seed, angles = self._draws(B)
+        parts = [np.asarray(ids, np.int32), jit, flips.reshape(-1)]
+        if angles is not None:      # the 8-byte values first: every view below stays aligned
+            parts = [cs.numpy().reshape(-1) for cs in (ops.rotate_tiles_cs(angles), ops.pack_locs_cs(angles))] + parts
+        buf = torch.from_numpy(np.concatenate([p.view(np.uint8) for p in parts])).to(dev)
+        views, at = [], 0
+        for p in parts:
+            views.append(buf[at:at + p.nbytes])
+            at += p.nbytes
+        dflips, djit, dids = views[-1].view(B, 2), views[-2].view(torch.float32), views[-3].view(torch.int32)
+        xs = ops.augment_tiles_indexed(res["store"], dids, dflips, djit, None, NOISESV, seed)
+        cs = None
+        if angles is not None:
+            xs = ops.rotate_tiles(xs, None, cs=views[0].view(torch.float64).view(B, 2))
+            cs = views[1].view(torch.float32).view(B, 2)
+        locs, counts = ops.pack_locs(res["rows"], res["offsets"], dids, dflips, size=HEATMAPSIZE, K=MAXTAGLEN,
+                                     trunc=True, cs=cs)
+        ys = ops.render_center_targets(locs, counts, HEATMAPSIZE, THRESHOLDIOU)
         return {"xs": [xs], "ys": ys}
 
     def __getitem__(self, index):
