@@ -34,7 +34,7 @@ class BasicBlock(torch.nn.Module):
 
     def forward(self, x):
         """x: NHWC activation (compute dtype) -> NHWC activation."""
-        return blocks.BasicBlockFn.apply(x, self.conv1.weight, self)
+        return blocks.ResidualFn.apply(x, self.conv1.weight, self)
 
 
 class Bottleneck(torch.nn.Module):
@@ -54,7 +54,7 @@ class Bottleneck(torch.nn.Module):
         self.stride = stride
 
     def forward(self, x):
-        return blocks.BottleneckFn.apply(x, self.conv1.weight, self)
+        return blocks.ResidualFn.apply(x, self.conv1.weight, self)
 
 
 class ResNetTerminal(BackboneTerminal):

@@ -2,8 +2,8 @@
 
 Each Function runs one reference module group entirely on libscdhip kernels:
   StemFn        preprocess: Conv2d(1,64,7,s2,p3)+BN+ReLU+MaxPool(3,2,1)   residuals.py:209-216
-  BasicBlockFn  BasicBlock (+downsample)                                  residuals.py:84-120, 256-271
-  BottleneckFn  Bottleneck (+downsample)                                  residuals.py:122-165
+  ResidualFn    BasicBlock / Bottleneck (+downsample): one chain over the   residuals.py:84-165, 256-271
+                block's own conv1..conv3
   DeconvBNFn    ConvTranspose2d(k4,s2,p1,no bias)+BN+ReLU                 residuals.py:286-310
   ConvBNFn      Convolution (conv+BN+ReLU) / conv+BN                      convolutions.py:25-49
   HeadsFn       all CenterNet terminals fused: one 3x3 GEMM with N = sum of
@@ -12,6 +12,9 @@ Each Function runs one reference module group entirely on libscdhip kernels:
 Parameter gradients are accumulated straight into ``param.grad`` (created on demand;
 with FlatAdam/FlatDDP they are views of one flat buffer), so the Functions return None
 for parameter inputs.  Activations between Functions are NHWC in the model's compute dtype.
+
+Every library launch is an ``ops`` function; what the folded inference path (scdhip.infer) shares with training -- the
+stem's and the heads' forward dispatch -- is ``ops.stem_fwd`` / ``ops.heads_fwd``.
 """
 import os
 
@@ -55,13 +58,12 @@ def _train_bn_conv(x, conv, bn, stride, pad, training, timer=None):
     return y, ops.bn_finalize(bn, stats, C, y.numel() // C, training)
 
 
-def _conv1_and_downsample(x, blk, conv1, bn1, s1, pad1, sd):
+def _conv1_and_downsample(x, dconv, bnd, conv1, bn1, s1, pad1, sd):
     """A block's first conv and its downsample conv (both read only the block input; residuals.py:99-120,
     145-165), then both BN finalizes together: with SyncBN one all-reduce for the two layers."""
-    bnd = blk.downsample[1]
-    C1, Cd = conv1.weight.shape[0], blk.downsample[0].weight.shape[0]
+    C1, Cd = conv1.weight.shape[0], dconv.weight.shape[0]
     y1, s1st = _conv_stats(x, conv1, bn1, s1, pad1, True)
-    yd, sdst = _conv_stats(x, blk.downsample[0], bnd, sd, 0, True)
+    yd, sdst = _conv_stats(x, dconv, bnd, sd, 0, True)
     st1, std = ops.bn_finalize_pair(bn1, s1st, C1, y1.numel() // C1, bnd, sdst, Cd, yd.numel() // Cd)
     return y1, st1, yd, std
 
@@ -85,19 +87,9 @@ class StemFn(torch.autograd.Function):
         training = bn.training
         C = conv.weight.shape[0]
         stats = ops.bn_stats(bn, "fwd") if training else None
-        ref_geom = tuple(conv.weight.shape) == (64, 1, 7, 7) and conv.stride[0] == 2 and conv.padding[0] == 3
-        direct = ops.stem_direct_ok(x, dtype) and ref_geom
-        if direct:
-            # direct 7x7/s2 conv: the tap tile is built in LDS from the input patch (no column tensor)
-            x = _c(x)
-            wpk = ops.pack_weight(conv.weight, dtype, 0, ldp=64)
-            y = ops.stem_conv_fwd(x, wpk, stats=stats)
-            cols = x
-        else:
-            cols = ops.im2col_stem(x, dtype, kh=conv.weight.shape[2], kw=conv.weight.shape[3],
-                                   stride=conv.stride[0], pad=conv.padding[0])
-            wp = ops.pack_weight(conv.weight, dtype, 0, ldp=cols.shape[-1])
-            y = ops.conv_fwd(cols, wp, C, 1, 1, 1, 0, stats=stats)
+        wpk = ops.pack_weight(conv.weight, dtype, 0, ldp=64)
+        geom = tuple(conv.weight.shape) + (conv.stride[0], conv.padding[0])
+        y, cols, direct = ops.stem_fwd(x, wpk, geom, dtype, stats)
         st = ops.bn_finalize(bn, stats, C, y.numel() // C, training)
         out, am = ops.stem_pool_fwd(y, st)
         ctx.save_for_backward(cols, y, am)
@@ -125,125 +117,84 @@ class StemFn(torch.autograd.Function):
         return None, None, None, None, None
 
 
-class BasicBlockFn(torch.autograd.Function):
+def _block_layers(blk):
+    """(conv, bn, weight, (kh, kw, stride, pad)) of a BasicBlock's / Bottleneck's main branch, in order (the walk of
+    infer.FoldedBlock): the geometry is the Conv2d modules' own."""
+    mods = [(blk.conv1, blk.bn1), (blk.conv2, blk.bn2)]
+    if "conv3" in blk._modules:
+        mods.append((blk.conv3, blk.bn3))
+    return [(c, bn, c.weight, (c.kernel_size[0], c.kernel_size[1], c.stride[0], c.padding[0])) for c, bn in mods]
+
+
+class ResidualFn(torch.autograd.Function):
+    """BasicBlock (two convs) and Bottleneck (three): conv + BN + ReLU down the main branch, the last BN joined with
+    the identity or with the 1x1 downsample conv's BN, then the ReLU."""
+
     @staticmethod
     def forward(ctx, x, w1, blk):
         tr = blk.training
-        s = blk.stride
+        layers = _block_layers(blk)
+        dconv, dbn = blk.downsample if blk.downsample is not None else (None, None)
         yd = std = None
-        if tr and blk.downsample is not None:
-            y1, st1, yd, std = _conv1_and_downsample(x, blk, blk.conv1, blk.bn1, s, 1, s)
-        else:
-            y1, st1 = _train_bn_conv(x, blk.conv1, blk.bn1, s, 1, tr)
-        a1 = ops.bn_apply(y1, st1, True)
-        y2, st2 = _train_bn_conv(a1, blk.conv2, blk.bn2, 1, 1, tr)
-        if blk.downsample is not None:
+        saved, sts, a = [], [], x               # saved: each conv's input and pre-BN output
+        for i, (conv, bn, _, (_, _, s, p)) in enumerate(layers):
+            if i == 0 and tr and dconv is not None:
+                y, st, yd, std = _conv1_and_downsample(x, dconv, dbn, conv, bn, s, p, dconv.stride[0])
+            else:
+                y, st = _train_bn_conv(a, conv, bn, s, p, tr)
+            saved += [a, y]
+            sts.append(st)
+            if i + 1 < len(layers):
+                a = ops.bn_apply(y, st, True)
+        if dconv is not None:
             if yd is None:                      # eval: the downsample conv after the main branch
-                yd, std = _train_bn_conv(x, blk.downsample[0], blk.downsample[1], s, 0, tr)
-            out = ops.bn_apply(y2, st2, True, res=yd, rst=std)
+                yd, std = _train_bn_conv(x, dconv, dbn, dconv.stride[0], 0, tr)
+            out = ops.bn_apply(y, st, True, res=yd, rst=std)
         else:
-            out = ops.bn_apply(y2, st2, True, res=x)
-        ctx.save_for_backward(x, y1, a1, y2, yd, out)
-        ctx.sts = (st1, st2, std)
-        ctx.blk = blk
+            out = ops.bn_apply(y, st, True, res=x)
+        ctx.save_for_backward(*saved, yd, out)
+        ctx.sts = (sts, std)
+        ctx.blk, ctx.layers, ctx.down = blk, layers, (dconv, dbn)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        x, y1, a1, y2, yd, out = ctx.saved_tensors
-        st1, st2, std = ctx.sts
-        blk = ctx.blk
-        dout = _c(dout)
-        s = blk.stride
-        N, H, W, Cin = x.shape
-        C = blk.conv1.weight.shape[0]
+        *saved, yd, out = ctx.saved_tensors
+        sts, std = ctx.sts
+        layers, (dconv, dbn) = ctx.layers, ctx.down
+        ins, ys = saved[0::2], saved[1::2]      # conv i reads ins[i] (ins[0] is the block input) and writes ys[i]
+        x = ins[0]
+        _, H, W, Cin = x.shape
         dx = dyd = None
-        w2 = blk.conv2.weight
-        if blk.downsample is not None:
-            dy2, dyd = ops.bn_backward_pair(blk.bn2, st2, y2, blk.downsample[1], std, yd, dout, out)
-            wd = blk.downsample[0].weight
-            gd, g2 = ops.grad_of(wd), ops.grad_of(w2)      # (before the ordering: may zero-fill on this stream)
+
+        def wgrad(i, dy, dst):
+            ops.conv_wgrad(dy, ins[i], *layers[i][3], dst, _conv_ld(layers[i][2]))
+
+        n = len(layers) - 1
+        _, bnn, wn, _ = layers[n]
+        if dconv is not None:
+            dy, dyd = ops.bn_backward_pair(bnn, sts[n], ys[n], dbn, std, yd, _c(dout), out)
+            wd = dconv.weight
+            gd, gn = ops.grad_of(wd), ops.grad_of(wn)      # (before the ordering: may zero-fill on this stream)
             with ops.side_batch():          # both weight gradients behind one side-stream ordering
-                ops.conv_wgrad(dyd, x, 1, 1, s, 0, gd, _conv_ld(wd))
-                ops.conv_wgrad(dy2, a1, 3, 3, 1, 1, g2, _conv_ld(w2))
+                ops.conv_wgrad(dyd, x, 1, 1, dconv.stride[0], 0, gd, _conv_ld(wd))
+                wgrad(n, dy, gn)
         else:
             dx = torch.empty_like(x)
-            dy2 = ops.bn_backward(blk.bn2, st2, dout, y2, mask=out, dz_out=dx)
-            ops.conv_wgrad(dy2, a1, 3, 3, 1, 1, ops.grad_of(w2), _conv_ld(w2))
-        dy1 = _dgrad_bn_relu_bwd(dy2, ops.pack_weight(w2, x.dtype, 1), C, a1.shape[1], a1.shape[2], 3, 3, 1, 1,
-                                 blk.bn1, st1, y1)
-        w1 = blk.conv1.weight
-        ops.conv_wgrad(dy1, x, 3, 3, s, 1, ops.grad_of(w1), _conv_ld(w1))
-        dx = ops.conv_dgrad_w(dy1, w1, H, W, s, 1, out=dx, accumulate=dx is not None)
+            dy = ops.bn_backward(bnn, sts[n], _c(dout), ys[n], mask=out, dz_out=dx)
+            wgrad(n, dy, ops.grad_of(wn))
+        for i in range(n, 0, -1):
+            _, _, w, geom = layers[i]
+            dy = _dgrad_bn_relu_bwd(dy, ops.pack_weight(w, x.dtype, 1), w.shape[1], ins[i].shape[1], ins[i].shape[2],
+                                    *geom, layers[i - 1][1], sts[i - 1], ys[i - 1])
+            wgrad(i - 1, dy, ops.grad_of(layers[i - 1][2]))
+        _, _, w1, (_, _, s1, p1) = layers[0]
+        dx = ops.conv_dgrad_w(dy, w1, H, W, s1, p1, out=dx, accumulate=dx is not None)
         if dyd is not None:
             # the downsample's input gradient last: += over the pixels its 1x1 taps reach only (one in four at stride 2)
-            ops.conv_dgrad(dyd, ops.pack_weight(blk.downsample[0].weight, x.dtype, 1), Cin, H, W, 1, 1, s, 0, out=dx,
+            ops.conv_dgrad(dyd, ops.pack_weight(wd, x.dtype, 1), Cin, H, W, 1, 1, dconv.stride[0], 0, out=dx,
                            accumulate=True)
-        grads_ready(blk)
-        return dx, None, None
-
-
-class BottleneckFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, w1, blk):
-        tr = blk.training
-        s = blk.stride
-        yd = std = None
-        if tr and blk.downsample is not None:
-            y1, st1, yd, std = _conv1_and_downsample(x, blk, blk.conv1, blk.bn1, 1, 0, s)
-        else:
-            y1, st1 = _train_bn_conv(x, blk.conv1, blk.bn1, 1, 0, tr)
-        a1 = ops.bn_apply(y1, st1, True)
-        y2, st2 = _train_bn_conv(a1, blk.conv2, blk.bn2, s, 1, tr)
-        a2 = ops.bn_apply(y2, st2, True)
-        y3, st3 = _train_bn_conv(a2, blk.conv3, blk.bn3, 1, 0, tr)
-        if blk.downsample is not None:
-            if yd is None:                      # eval: the downsample conv after the main branch
-                yd, std = _train_bn_conv(x, blk.downsample[0], blk.downsample[1], s, 0, tr)
-            out = ops.bn_apply(y3, st3, True, res=yd, rst=std)
-        else:
-            out = ops.bn_apply(y3, st3, True, res=x)
-        ctx.save_for_backward(x, y1, a1, y2, a2, y3, yd, out)
-        ctx.sts = (st1, st2, st3, std)
-        ctx.blk = blk
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        x, y1, a1, y2, a2, y3, yd, out = ctx.saved_tensors
-        st1, st2, st3, std = ctx.sts
-        blk = ctx.blk
-        dout = _c(dout)
-        s = blk.stride
-        N, H, W, Cin = x.shape
-        P = blk.conv1.weight.shape[0]
-        dx = dyd = None
-        w3 = blk.conv3.weight
-        if blk.downsample is not None:
-            dy3, dyd = ops.bn_backward_pair(blk.bn3, st3, y3, blk.downsample[1], std, yd, dout, out)
-            wd = blk.downsample[0].weight
-            gd, g3 = ops.grad_of(wd), ops.grad_of(w3)      # (before the ordering: may zero-fill on this stream)
-            with ops.side_batch():          # both weight gradients behind one side-stream ordering
-                ops.conv_wgrad(dyd, x, 1, 1, s, 0, gd, _conv_ld(wd))
-                ops.conv_wgrad(dy3, a2, 1, 1, 1, 0, g3, _conv_ld(w3))
-        else:
-            dx = torch.empty_like(x)
-            dy3 = ops.bn_backward(blk.bn3, st3, dout, y3, mask=out, dz_out=dx)
-            ops.conv_wgrad(dy3, a2, 1, 1, 1, 0, ops.grad_of(w3), _conv_ld(w3))
-        dy2 = _dgrad_bn_relu_bwd(dy3, ops.pack_weight(w3, x.dtype, 1), P, a2.shape[1], a2.shape[2], 1, 1, 1, 0,
-                                 blk.bn2, st2, y2)
-        w2 = blk.conv2.weight
-        ops.conv_wgrad(dy2, a1, 3, 3, s, 1, ops.grad_of(w2), _conv_ld(w2))
-        dy1 = _dgrad_bn_relu_bwd(dy2, ops.pack_weight(w2, x.dtype, 1), P, a1.shape[1], a1.shape[2], 3, 3, s, 1,
-                                 blk.bn1, st1, y1)
-        w1 = blk.conv1.weight
-        ops.conv_wgrad(dy1, x, 1, 1, 1, 0, ops.grad_of(w1), _conv_ld(w1))
-        dx = ops.conv_dgrad(dy1, ops.pack_weight(w1, x.dtype, 1), Cin, H, W, 1, 1, 1, 0, out=dx,
-                            accumulate=dx is not None)
-        if dyd is not None:
-            ops.conv_dgrad(dyd, ops.pack_weight(blk.downsample[0].weight, x.dtype, 1), Cin, H, W, 1, 1, s, 0, out=dx,
-                           accumulate=True)
-        grads_ready(blk)
+        grads_ready(ctx.blk)
         return dx, None, None
 
 
@@ -323,43 +274,20 @@ class HeadsFn(torch.autograd.Function):
         N, H, W, Cin = feat.shape
         w0s = [h[0].weight for h in heads]
         b0 = torch.cat([h[0].bias for h in heads], 0)
-        Hd = heads[0][0].weight.shape[0]
-        Ct = sum(w.shape[0] for w in w0s)
-        od = [h[2].weight.shape[0] for h in heads]
-        outs = [torch.empty(N, o, H, W, device=feat.device, dtype=torch.float32) for o in od]
+        hd = ops.HeadsDesc([h[2].weight for h in heads], [h[2].bias for h in heads])
         wp = ops.pack_concat(w0s, feat.dtype, 0)
-        w1s = ops.L.ptr_array([h[2].weight.data_ptr() for h in heads])
-        b1s = ops.L.ptr_array([h[2].bias.data_ptr() for h in heads])
-        optrs = ops.L.ptr_array([o.data_ptr() for o in outs])
-        odarr = ops.L.int_array(od)
         hint = ops.take_sparse_hint()
-        ctx.keep = None
-        if Hd == 128 and len(heads) <= 4 and max(od) <= 4:
-            # tails fused into the GEMM epilogue (one launch, hidden tensor read once)
-            hid = torch.empty(N, H, W, Ct, device=feat.device, dtype=feat.dtype)
-            keep = None
-            if (hint is not None and len(heads) >= 2 and Cin <= 256 and (len(heads) - 1) * Hd <= 256
-                    and hint.dim() == 2 and hint.shape[0] == N):
-                # the loss gathers the size / offset outputs at `hint` only: their hidden channels are stored there
-                keep = ops.heads_keep_map(hint, N, H * W)
-                ctx.keep = (hint, hint._version)
-            args = (ops.dt(feat), ops.ptr(feat), ops.ptr(wp), ops.ptr(hid), ops.ptr(b0), N, H, W, Cin, len(heads),
-                    odarr, w1s, b1s)
-            t0 = ops.LaunchTimer.record("heads_gemm")
-            ops.L.call("scd_conv_gemm_heads_keep", *args, optrs, ops.ptr(keep) if keep is not None else None, Hd,
-                       ops.stream())
-            ops.LaunchTimer.close("heads_gemm", t0)
-            if keep is not None:
-                # everything needed to store the whole hidden tensor again (a dense backward after all)
-                scratch = [torch.empty_like(o) for o in outs]
-                ctx.refill = (args, ops.L.ptr_array([o.data_ptr() for o in scratch]), wp, b0, scratch)
-        else:
-            hid = ops.conv_fwd(feat, wp, Ct, 3, 3, 1, 1, bias=b0, relu=True)
-            ops.L.call("scd_heads_fwd", ops.dt(hid), ops.ptr(hid), N, H * W, len(heads), Hd, odarr, w1s, b1s, optrs,
-                       ops.stream())
+        keep = ctx.keep = ctx.refill = None
+        if (hd.fused and hint is not None and hd.nh >= 2 and Cin <= 256 and (hd.nh - 1) * hd.Hd <= 256
+                and hint.dim() == 2 and hint.shape[0] == N):
+            # the loss gathers the size / offset outputs at `hint` only: their hidden channels are stored there
+            keep = ops.heads_keep_map(hint, N, H * W)
+            ctx.keep = (hint, hint._version)
+            ctx.refill = (wp, b0)       # what storing the whole hidden tensor again needs (a dense backward after all)
+        hid, outs = ops.heads_fwd(feat, wp, b0, hd, keep)
         ctx.save_for_backward(feat, hid)
         ctx.w0s = w0s
-        ctx.heads, ctx.od, ctx.Hd = heads, od, Hd
+        ctx.heads, ctx.hd = heads, hd
         ctx.prod = ops.bn_producer(feat)        # the deconv BN+ReLU: its backward sums come from our dgrad
         return tuple(outs)
 
@@ -367,54 +295,41 @@ class HeadsFn(torch.autograd.Function):
     def backward(ctx, *douts):
         feat, hid = ctx.saved_tensors
         w0s = ctx.w0s
-        heads, od, Hd = ctx.heads, ctx.od, ctx.Hd
+        heads, hd = ctx.heads, ctx.hd
+        Hd, nh = hd.Hd, hd.nh
         N, H, W, Cin = feat.shape
-        nh = len(heads)
         douts = [(_c(d) if d is not None else torch.zeros(N, o, H, W, device=feat.device))
-                 for d, o in zip(douts, od)]
+                 for d, o in zip(douts, hd.od)]
         # fp16: the backward below runs on loss-scaled gradients (ops.LossScale: the repack multiplies the head
         # gradients by S), unscaled into every .grad
         S = ops.begin_loss_scale(feat.dtype)
-        dptrs = ops.L.ptr_array([d.data_ptr() for d in douts])
-        odarr = ops.L.int_array(od)
+        dptrs = ops.tensor_ptrs(douts)
         nd = HeadsFn._dense_prefix(douts, Hd, Cin)
         if ctx.keep is not None:
             inds = ops.sparse_grad_inds(douts[-1]) if nd == 1 else None
             if inds is None or inds is not ctx.keep[0] or inds._version != ctx.keep[1]:
                 # the forward kept the size / offset hidden channels at other pixels only: store them all
-                args, optrs, _, _, _ = ctx.refill
-                ops.L.call("scd_conv_gemm_heads_keep", *args, optrs, None, 0, ops.stream())
+                ops.heads_refill(feat, *ctx.refill, hd, hid)
             ctx.refill = None
         if nd < nh:
-            return HeadsFn._backward_sparse(ctx, douts, dptrs, odarr, nd, S)
-        dhid = torch.empty_like(hid)
-        acc = ops.persistent_zeros(heads[0][2].weight, "_scd_heads_acc",
-                                   ops.L.lib().scd_heads_bwd_accsize(nh, Hd, odarr) // 8, torch.float64)
-        packed = torch.empty(N * H * W * nh * 4, device=feat.device)
-        ops.L.call("scd_heads_bwd_packed", ops.dt(hid), ops.ptr(hid), N, H * W, nh, Hd, odarr,
-                   ops.L.ptr_array([h[2].weight.data_ptr() for h in heads]), dptrs, float(S), ops.ptr(packed),
-                   ops.ptr(dhid), ops.ptr(acc), ops.stream())
-        ops.L.call("scd_heads_bwd_weight_finalize", ops.ptr(acc), nh, Hd, odarr,
-                   ops.L.ptr_array([ops.grad_of(h[2].weight).data_ptr() for h in heads]),
-                   ops.L.ptr_array([ops.grad_of(h[2].bias).data_ptr() for h in heads]),
-                   ops.L.ptr_array([ops.grad_of(h[0].bias).data_ptr() for h in heads]), 1, 1.0 / S, ops.stream())
+            return HeadsFn._backward_sparse(ctx, douts, dptrs, hd.odarr, nd, S)
+        dhid = ops.heads_bwd_packed(hid, hd, dptrs, S)
+        ops.heads_bwd_weight_finalize(hd, [h[0].bias for h in heads], S)
         ld = (Cin * 9, 9, 1)
         rows = [(i * Hd, (i + 1) * Hd, ops.grad_of(h[0].weight), ld) for i, h in enumerate(heads)]
         ops.conv_wgrad(dhid, feat, 3, 3, 1, 1, None, None, rows=rows)
+        # feat's gradient shared with other consumers (ops.share_grad): write into / start the one buffer, and no
+        # BN-backward sums from this epilogue (they would cover this consumer's part only)
         slot = ops.shared_grad_slot(feat)
-        if slot is not None:
-            # feat's gradient is shared with other consumers (ops.share_grad): write into / start the one buffer
-            # (no BN-backward sums from this epilogue: they would cover this consumer's part only)
-            dfeat = ops.conv_dgrad(dhid, ops.pack_concat(w0s, feat.dtype, 1), Cin, H, W, 3, 3, 1, 1, out=slot[1],
-                                   accumulate=slot[1] is not None)
-            grads_ready(*[m for h in heads for m in h if isinstance(m, torch.nn.Module)])
-            return ops.shared_grad_out(feat, slot, dfeat if slot[1] is None else None), None, None
-        fuse = ctx.prod is not None and feat.dtype in ops.HALF
-        dfeat = ops.conv_dgrad(dhid, ops.pack_concat(w0s, feat.dtype, 1), Cin, H, W, 3, 3, 1, 1,
-                               bn_bwd=ops.fused_bn_bwd_args(ctx.prod) if fuse else None)
+        prev = slot[1] if slot is not None else None
+        fuse = slot is None and ctx.prod is not None and feat.dtype in ops.HALF
+        dfeat = ops.conv_dgrad(dhid, ops.pack_concat(w0s, feat.dtype, 1), Cin, H, W, 3, 3, 1, 1, out=prev,
+                               accumulate=prev is not None, bn_bwd=ops.fused_bn_bwd_args(ctx.prod) if fuse else None)
         if fuse:
             ops.mark_bn_bwd_fused(ctx.prod[0], dfeat)
         grads_ready(*[m for h in heads for m in h if isinstance(m, torch.nn.Module)])
+        if slot is not None:
+            return ops.shared_grad_out(feat, slot, dfeat if prev is None else None), None, None
         return dfeat, None, None
 
     @staticmethod
@@ -437,31 +352,16 @@ class HeadsFn(torch.autograd.Function):
         gradient (a GEMM over those pixels' im2col rows) and the 3x3 input gradient (a small GEMM then a gather
         into the dense input gradient) run over that pixel set (scd_heads_sparse_bwd / scd_heads_sparse_fixup)."""
         feat, hid = ctx.saved_tensors
-        w0s, heads, od, Hd = ctx.w0s, ctx.heads, ctx.od, ctx.Hd
+        w0s, heads, hd = ctx.w0s, ctx.heads, ctx.hd
+        Hd, nh = hd.Hd, hd.nh
         N, H, W, Cin = feat.shape
-        nh = len(heads)
-        dev, dt = feat.device, feat.dtype
+        dt = feat.dtype
         inds = ops.sparse_grad_inds(douts[-1])
-        K = inds.shape[1]
-        Sl = N * K                                     # slots
+        Sl = N * inds.shape[1]                         # slots
         Cs = (nh - nd) * Hd
-        w1s = ops.L.ptr_array([h[2].weight.data_ptr() for h in heads])
-        acc = ops.persistent_zeros(heads[0][2].weight, "_scd_heads_acc",
-                                   ops.L.lib().scd_heads_bwd_accsize(nh, Hd, odarr) // 8, torch.float64)
-        dh_dense = torch.empty(N, H, W, nd * Hd, device=dev, dtype=dt)
-        packed = torch.empty(N * H * W * nd * 4, device=dev)
-        ops.L.call("scd_heads_bwd_packed_split", ops.dt(hid), ops.ptr(hid), N, H * W, nh, Hd, odarr, nd, w1s, dptrs,
-                   float(S), ops.ptr(packed), ops.ptr(dh_dense), ops.ptr(acc), ops.stream())
-        dhid_s = torch.empty(Sl, Cs, device=dev, dtype=dt)
-        xcol = torch.empty(Sl, Cin * 9, device=dev, dtype=dt)
-        slotmap, ownermap = ops.sparse_maps(dev, N * H * W)
-        ops.L.call("scd_heads_sparse_bwd", ops.dt(hid), ops.ptr(hid), ops.ptr(feat), N, H, W, Cin, nh, Hd, odarr, nd,
-                   w1s, dptrs, float(S), ops.ptr(inds), K, ops.ptr(dhid_s), ops.ptr(xcol), ops.ptr(acc),
-                   ops.ptr(slotmap), ops.ptr(ownermap), ops.stream())
-        ops.L.call("scd_heads_bwd_weight_finalize", ops.ptr(acc), nh, Hd, odarr,
-                   ops.L.ptr_array([ops.grad_of(h[2].weight).data_ptr() for h in heads]),
-                   ops.L.ptr_array([ops.grad_of(h[2].bias).data_ptr() for h in heads]),
-                   ops.L.ptr_array([ops.grad_of(h[0].bias).data_ptr() for h in heads]), 1, 1.0 / S, ops.stream())
+        dh_dense = ops.heads_bwd_packed(hid, hd, dptrs, S, nd)
+        dhid_s, xcol, slotmap, ownermap = ops.heads_sparse_bwd(hid, feat, hd, nd, dptrs, S, inds)
+        ops.heads_bwd_weight_finalize(hd, [h[0].bias for h in heads], S)
         # weight gradients: dense heads over every pixel, sparse heads over the slots' im2col rows (a 1x1 GEMM whose
         # Cin*9 columns are the OIHW rows of their 3x3 weights)
         ld = (Cin * 9, 9, 1)
@@ -482,14 +382,7 @@ class HeadsFn(torch.autograd.Function):
         dfeat = ops.conv_dgrad(dh_dense, ops.pack_concat(w0s[:nd], dt, 1), Cin, H, W, 3, 3, 1, 1, bn_bwd=bn_args)
         wt_s = ops.pack_concat(w0s[nd:], dt, 2)          # [tap][ci][c] rows: W0^T of the sparse heads, tap-major
         cols = ops.conv_fwd(dhid_s.view(1, 1, Sl, Cs), wt_s, 9 * Cin, 1, 1, 1, 0)
-        if fuse:
-            st, ybn, bstats = bn_args
-            bn_ptrs = (ops.ptr(ybn), ops.ptr(st.mean), ops.ptr(st.invstd), ops.ptr(st.scale), ops.ptr(st.shift),
-                       ops.ptr(bstats))
-        else:
-            bn_ptrs = (None,) * 6
-        ops.L.call("scd_heads_sparse_fixup", ops.dt(dfeat), ops.ptr(dfeat), ops.ptr(cols), N, H, W, Cin, ops.ptr(inds),
-                   K, ops.ptr(slotmap), ops.ptr(ownermap), *bn_ptrs, ops.stream())
+        ops.heads_sparse_fixup(dfeat, cols, inds, slotmap, ownermap, bn_args)
         mods = [m for h in heads for m in h if isinstance(m, torch.nn.Module)]
         if fuse:
             ops.mark_bn_bwd_fused(ctx.prod[0], dfeat)

@@ -9,8 +9,8 @@ store.  The eval path of the training forward (a GEMM that writes the pre-BN out
 steady-state folded forward makes no ``scd_bn_*`` and no ``scd_pack_*`` call, runs under ``no_grad`` and saves nothing.
 
 The stem keeps its kernels (raw-weight stem conv, then ``scd_stem_pool_fwd``, which already fuses the BN scale / shift,
-the ReLU and the pool); the heads and the decode are the library calls of ``blocks.HeadsFn.forward`` and the model's
-decoder, without the training path's keep map.
+the ReLU and the pool) behind ``ops.stem_fwd``, the dispatch ``blocks.StemFn`` uses; the heads are ``ops.heads_fwd``, as
+in ``blocks.HeadsFn.forward`` but without the training path's keep map, and the decode is the model's decoder.
 """
 import torch
 
@@ -121,9 +121,7 @@ class _Stem:
     def __init__(self, conv, bn, dtype):
         _need_cuda(conv.weight, "stem")
         self.dtype = dtype
-        self.geom = (conv.weight.shape[2], conv.weight.shape[3], conv.stride[0], conv.padding[0])
-        self.ref_geom = tuple(conv.weight.shape) == (64, 1, 7, 7) and conv.stride[0] == 2 and conv.padding[0] == 3
-        self.C = conv.weight.shape[0]
+        self.geom = tuple(conv.weight.shape) + (conv.stride[0], conv.padding[0])
         self.w = _pack(conv.weight, dtype, 0, ldp=64)
         s = bn.weight.detach().double() / torch.sqrt(bn.running_var.detach().double() + bn.eps)
         self.st = ops.BNState()
@@ -131,13 +129,7 @@ class _Stem:
         self.st.shift = (bn.bias.detach().double() - bn.running_mean.detach().double() * s).float().contiguous()
 
     def __call__(self, x):
-        x = x.float().contiguous()
-        if self.ref_geom and ops.stem_direct_ok(x, self.dtype):
-            y = ops.stem_conv_fwd(x, self.w)
-        else:
-            kh, kw, s, p = self.geom
-            cols = ops.im2col_stem(x, self.dtype, kh=kh, kw=kw, stride=s, pad=p)
-            y = ops.conv_fwd(cols, self.w, self.C, 1, 1, 1, 0)
+        y, _, _ = ops.stem_fwd(x.float().contiguous(), self.w, self.geom, self.dtype)
         return ops.stem_pool_fwd(y, self.st)[0]
 
 
@@ -146,31 +138,13 @@ class _Heads:
 
     def __init__(self, names, mods, dtype):
         self.names = names
-        self.Hd = mods[0][0].weight.shape[0]
-        self.od = [m[2].weight.shape[0] for m in mods]
         self.w0 = _pack(torch.cat([m[0].weight.detach() for m in mods], 0), dtype, 0)
         self.b0 = torch.cat([m[0].bias.detach().float() for m in mods], 0).contiguous()
-        self.w1 = [m[2].weight.detach().float().clone().contiguous() for m in mods]
-        self.b1 = [m[2].bias.detach().float().clone().contiguous() for m in mods]
-        self.w1p = ops.L.ptr_array([w.data_ptr() for w in self.w1])
-        self.b1p = ops.L.ptr_array([b.data_ptr() for b in self.b1])
-        self.odarr = ops.L.int_array(self.od)
+        self.desc = ops.HeadsDesc([m[2].weight.detach().float().clone().contiguous() for m in mods],
+                                  [m[2].bias.detach().float().clone().contiguous() for m in mods])
 
     def __call__(self, feat):
-        N, H, W, Cin = feat.shape
-        outs = [torch.empty(N, o, H, W, device=feat.device, dtype=torch.float32) for o in self.od]
-        optrs = ops.L.ptr_array([o.data_ptr() for o in outs])
-        nh, Ct = len(self.od), len(self.od) * self.Hd
-        if self.Hd == 128 and nh <= 4 and max(self.od) <= 4:
-            hid = torch.empty(N, H, W, Ct, device=feat.device, dtype=feat.dtype)
-            ops.L.call("scd_conv_gemm_heads_keep", ops.dt(feat), ops.ptr(feat), ops.ptr(self.w0), ops.ptr(hid),
-                       ops.ptr(self.b0), N, H, W, Cin, nh, self.odarr, self.w1p, self.b1p, optrs, None, self.Hd,
-                       ops.stream())
-        else:
-            hid = ops.conv_fwd(feat, self.w0, Ct, 3, 3, 1, 1, bias=self.b0, relu=True)
-            ops.L.call("scd_heads_fwd", ops.dt(hid), ops.ptr(hid), N, H * W, nh, self.Hd, self.odarr, self.w1p,
-                       self.b1p, optrs, ops.stream())
-        return dict(zip(self.names, outs))
+        return dict(zip(self.names, ops.heads_fwd(feat, self.w0, self.b0, self.desc)[1]))
 
 
 class FoldedResNet(torch.nn.Module):

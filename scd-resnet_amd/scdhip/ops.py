@@ -1011,6 +1011,104 @@ def sparse_maps(dev, npix):
     return m
 
 
+def tensor_ptrs(ts):
+    return L.ptr_array([t.data_ptr() for t in ts])
+
+
+class HeadsDesc:
+    """What one call's heads launches share, from the 1x1 tails' weights `w1` and biases `b1` (kept alive): widths and
+    C arrays.  Built once per forward (scdhip.infer: once per fold) and used again by that forward's backward."""
+
+    def __init__(self, w1, b1):
+        self.w1, self.b1, self.nh, self.od, self.Hd = w1, b1, len(w1), [w.shape[0] for w in w1], w1[0].shape[1]
+        self.odarr, self.w1s, self.b1s = L.int_array(self.od), tensor_ptrs(w1), tensor_ptrs(b1)
+        # the tails run in the 3x3 GEMM's epilogue (scd_conv_gemm_heads_keep: one launch, hidden tensor read once)
+        self.fused = self.Hd == 128 and self.nh <= 4 and max(self.od) <= 4
+        self._acc = None
+
+    def acc(self):
+        """The persistent float64 accumulator of the tails' gradients (heads_bwd_weight_finalize zeroes it again)."""
+        if self._acc is None:
+            n = L.lib().scd_heads_bwd_accsize(self.nh, self.Hd, self.odarr) // 8
+            self._acc = persistent_zeros(self.w1[0], "_scd_heads_acc", n, torch.float64)
+        return self._acc
+
+
+def _heads_gemm(feat, wp, b0, hd, hid, outs, keep, keep_cols):
+    N, H, W, Cin = feat.shape
+    L.call("scd_conv_gemm_heads_keep", dt(feat), ptr(feat), ptr(wp), ptr(hid), ptr(b0), N, H, W, Cin, hd.nh, hd.odarr,
+           hd.w1s, hd.b1s, tensor_ptrs(outs), ptr(keep) if keep is not None else None, keep_cols, stream())
+
+
+def heads_fwd(feat, wp, b0, hd, keep=None):
+    """hid = relu(conv3x3(feat, wp) + b0), wp = pack_concat(3x3 weights, mode 0), then the 1x1 tails -> (hid, [NCHW fp32
+    output per head]).  `keep` (heads_keep_map; fused launch only): heads 1.. store hid at the map's pixels only."""
+    N, H, W, _ = feat.shape
+    Ct = hd.nh * hd.Hd
+    outs = [torch.empty(N, o, H, W, device=feat.device, dtype=torch.float32) for o in hd.od]
+    if hd.fused:
+        hid = torch.empty(N, H, W, Ct, device=feat.device, dtype=feat.dtype)
+        t0 = LaunchTimer.record("heads_gemm")
+        _heads_gemm(feat, wp, b0, hd, hid, outs, keep, hd.Hd)
+        LaunchTimer.close("heads_gemm", t0)
+    else:
+        hid = conv_fwd(feat, wp, Ct, 3, 3, 1, 1, bias=b0, relu=True)
+        L.call("scd_heads_fwd", dt(hid), ptr(hid), N, H * W, hd.nh, hd.Hd, hd.odarr, hd.w1s, hd.b1s, tensor_ptrs(outs),
+               stream())
+    return hid, outs
+
+
+def heads_refill(feat, wp, b0, hd, hid):
+    """Store the whole hidden tensor again after a heads_fwd with a keep map: the fused launch without the map."""
+    N, H, W, _ = feat.shape
+    _heads_gemm(feat, wp, b0, hd, hid, [torch.empty(N, o, H, W, device=feat.device) for o in hd.od], None, 0)
+
+
+def heads_bwd_packed(hid, hd, dptrs, S, nd=None):
+    """The tails' backward from the output gradients `dptrs` (times S): the weight / bias sums into hd.acc(); returns
+    the hidden gradient of all heads (scd_heads_bwd_packed) or, with nd, of the heads [0, nd) (..._packed_split)."""
+    N, H, W, _ = hid.shape
+    n = hd.nh if nd is None else nd
+    dhid = torch.empty(N, H, W, n * hd.Hd, device=hid.device, dtype=hid.dtype)
+    packed = torch.empty(N * H * W * n * 4, device=hid.device)
+    name, split = ("scd_heads_bwd_packed", ()) if nd is None else ("scd_heads_bwd_packed_split", (nd,))
+    L.call(name, dt(hid), ptr(hid), N, H * W, hd.nh, hd.Hd, hd.odarr, *split, hd.w1s, dptrs, float(S), ptr(packed),
+           ptr(dhid), ptr(hd.acc()), stream())
+    return dhid
+
+
+def heads_sparse_bwd(hid, feat, hd, nd, dptrs, S, inds):
+    """The tails' backward of the heads [nd, nh) over the pixels inds[b][k] -> (dhid_s, xcol, slotmap, ownermap): the
+    hidden gradient and feat's im2col rows per slot (N*K of them), and the pixel maps for heads_sparse_fixup."""
+    N, H, W, Cin = feat.shape
+    K = inds.shape[1]
+    dhid_s = torch.empty(N * K, (hd.nh - nd) * hd.Hd, device=feat.device, dtype=feat.dtype)
+    xcol = torch.empty(N * K, Cin * 9, device=feat.device, dtype=feat.dtype)
+    slotmap, ownermap = sparse_maps(feat.device, N * H * W)
+    L.call("scd_heads_sparse_bwd", dt(hid), ptr(hid), ptr(feat), N, H, W, Cin, hd.nh, hd.Hd, hd.odarr, nd, hd.w1s,
+           dptrs, float(S), ptr(inds), K, ptr(dhid_s), ptr(xcol), ptr(hd.acc()), ptr(slotmap), ptr(ownermap), stream())
+    return dhid_s, xcol, slotmap, ownermap
+
+
+def heads_sparse_fixup(dfeat, cols, inds, slotmap, ownermap, bn_bwd=None):
+    """dfeat += the sparse heads' input gradient from their slots' 9 * Cin columns `cols`; restores both pixel maps.
+    bn_bwd: the fused_bn_bwd_args the dense heads' dgrad GEMM ran with."""
+    N, H, W, Cin = dfeat.shape
+    bn_ptrs = (None,) * 6
+    if bn_bwd is not None:
+        st, ybn, bstats = bn_bwd
+        bn_ptrs = (ptr(ybn), ptr(st.mean), ptr(st.invstd), ptr(st.scale), ptr(st.shift), ptr(bstats))
+    L.call("scd_heads_sparse_fixup", dt(dfeat), ptr(dfeat), ptr(cols), N, H, W, Cin, ptr(inds), inds.shape[1],
+           ptr(slotmap), ptr(ownermap), *bn_ptrs, stream())
+
+
+def heads_bwd_weight_finalize(hd, b0s, S):
+    """hd.acc() -> the gradients of the tails' weights and biases and of the 3x3 biases `b0s` (+=, times 1 / S)."""
+    L.call("scd_heads_bwd_weight_finalize", ptr(hd.acc()), hd.nh, hd.Hd, hd.odarr,
+           tensor_ptrs([grad_of(w) for w in hd.w1]), tensor_ptrs([grad_of(b) for b in hd.b1]),
+           tensor_ptrs([grad_of(b) for b in b0s]), 1, 1.0 / S, stream())
+
+
 # ------------------------------------------------------------------ weight gradients on a side stream
 #
 # Inside a backward pass the weight-gradient GEMMs (+ their split reductions) only feed the optimizer (and
@@ -1095,10 +1193,7 @@ def side_stream_for_comm(dev):
 
 
 def conv_wgrad(g, x, kh, kw, stride, pad, dst, ld, cvalid=None, accumulate=True, rows=None, red_taps=1):
-    _conv_wgrad_side(g, x, kh, kw, stride, pad, dst, ld, cvalid, accumulate, rows, red_taps)
-
-
-def _conv_wgrad_side(g, x, kh, kw, stride, pad, dst, ld, cvalid=None, accumulate=True, rows=None, red_taps=1):
+    """_conv_wgrad on the side stream (inside a backward pass), else on the current stream."""
     side = side_stream(g.device) if g.is_cuda else None
     if side is None:
         return _conv_wgrad(g, x, kh, kw, stride, pad, dst, ld, cvalid, accumulate, rows, red_taps)
@@ -1334,6 +1429,18 @@ def stem_conv_fwd(x, wpk, stats=None):
     y = torch.empty(N, Ho, Wo, 64, dtype=wpk.dtype, device=x.device)
     L.call("scd_stem_conv_fwd", dt(wpk), ptr(x), ptr(wpk), ptr(y), ptr(stats), N, H, W, Ho, Wo, stream())
     return y
+
+
+def stem_fwd(x, wpk, geom, dtype, stats=None):
+    """The stem conv of NCHW fp32 x -> (y, cols, direct); wpk = pack_weight(w, dtype, 0, ldp=64), geom = (Co, Ci, kh,
+    kw, stride, pad).  direct: the reference's Conv2d(1,64,7,s2,p3) where stem_direct_ok, the tap tile built in LDS
+    from the input patch (no column tensor; cols is the contiguous x); else im2col and a 1x1 GEMM over it."""
+    Co, _, kh, kw, stride, pad = geom
+    if stem_direct_ok(x, dtype) and geom == (64, 1, 7, 7, 2, 3):
+        x = _c(x)
+        return stem_conv_fwd(x, wpk, stats=stats), x, True
+    cols = im2col_stem(x, dtype, kh=kh, kw=kw, stride=stride, pad=pad)
+    return conv_fwd(cols, wpk, Co, 1, 1, 1, 0, stats=stats), cols, False
 
 
 def stem_out_count(x):
