@@ -369,6 +369,26 @@ int scd_scale_by_device(float* g, long n, const float* factors, int idx, const f
  * (0 where the centre is outside the map). threshold = the IoU threshold of the radius rule (0.5). */
 int scd_render_center_targets(const float* locs, const int* counts, int B, int K, int H, float threshold,
                               float* heat, uint8_t* mask, float* regr, int64_t* inds, void* stream);
+/* CornerNet training targets (CornerNetLoss reads ys[0], ys[3], ys[4]; the reference ships no corner encoder, the rule
+ * is this project's): one launch writes heat / mask / regr / inds exactly as scd_render_center_targets does
+ * for the same arguments (the same device functions, bit for bit) and the top-left and bottom-right maps tl, br
+ * (B,1,H,H) fp32.  For slot k < min(counts[b], K), in float32: dx = rintf(fabsf(majx)), dy = rintf(minl), top-left =
+ * (clip(ctx - dx, 0, H-1), clip(cty - dy, 0, H-1)), bottom-right = (clip(ctx + dx, 0, H-1), clip(cty + dy, 0, H-1)),
+ * each truncated to its cell and splatted with the centre's radius, sigma and clipped window, in slot order with the
+ * clip at 1 after every splat.  A corner is drawn only when the object's centre lies on the map and both of the
+ * corner's coordinates are finite (a NaN major axis draws no corner).  SCD_ERR_ARG and no launch for a NULL pointer,
+ * B < 1, K < 1, K > 64, H < 1 or H*H >= 2^31.  scd_render_corner_targets_split is the same with the split of the
+ * pixel work over the three maps named (SCD_ERR_ARG for an unknown one; every split gives the same bits):
+ * tools/corner_targets_bench.py times them, scd_render_corner_targets uses SCD_CORNER_SPLIT_DEFAULT. */
+#define SCD_CORNER_SPLIT_THREAD 0    /* grid (B, slices): a thread renders its pixel of all three maps */
+#define SCD_CORNER_SPLIT_GRID 1      /* grid (B, slices, 3): the map is a grid dimension */
+#define SCD_CORNER_SPLIT_DEFAULT SCD_CORNER_SPLIT_GRID     /* the faster one, profiles/corner_targets.txt */
+int scd_render_corner_targets(const float* locs, const int* counts, int B, int K, int H, float threshold,
+                              float* heat, float* tl, float* br, uint8_t* mask, float* regr, int64_t* inds,
+                              void* stream);
+int scd_render_corner_targets_split(const float* locs, const int* counts, int B, int K, int H, float threshold,
+                                    float* heat, float* tl, float* br, uint8_t* mask, float* regr, int64_t* inds,
+                                    int split, void* stream);
 /* SCD tile augmentation (datasets/scds/scdx16p100.py:416-441, datasets/argumentations.py:38-64):
  * out[b] = (flip(in[b]) - mean) / sqrt(var) * jitter[b] + noise * noise_sv, mean/var over the flipped tile (fp64
  * sums).  flips (B,2) u8 device [x (dim 2), y (dim 1)], nullable; jitter (B) device factors (1 + 0.05 g), nullable;

@@ -2,7 +2,7 @@
 
 Same default keys and the same overlay rule: a JSON config replaces only keys that already
 exist (configuration.py:150-153); string values may reference other keys as `{key}` format
-fields.  Four keys are added: ``computeDtype`` ("bf16" | "fp16" | "fp32"), the MFMA precision of the
+fields.  Five keys are added: ``computeDtype`` ("bf16" | "fp16" | "fp32"), the MFMA precision of the
 HIP path (the reference trains in fp32 without AMP), ``stepGraph`` (true | false, default false):
 replay the training step as a captured HIP graph after two eager steps (single-process runs;
 scdhip/graph.py -- measured slower than eager issue on ROCm 7), ``rotateAugmentation``
@@ -10,7 +10,9 @@ scdhip/graph.py -- measured slower than eager issue on ROCm 7), `
 drawn uniformly from [-value, value] (the reference holds this step switched off), and
 ``residentDataset`` (true | false, default false): the `.d` dataset plugins upload the whole archive (tiles and
 labels) to the device at the first training batch and build every batch there from the host's random draws
-(it raises when the archive does not fit into the device's free memory).
+(it raises when the archive does not fit into the device's free memory), and ``cornerTargets``
+(true | false, default false): the `.d` dataset plugins serve CornerNet's target layout [heat, mask, regr, tl, br],
+training batches and validation set alike, the corner maps rendered by scd_render_corner_targets.
 """
 import os
 
@@ -50,6 +52,7 @@ class Configuration:
         c["stepGraph"] = False
         c["rotateAugmentation"] = 0.0
         c["residentDataset"] = False
+        c["cornerTargets"] = False
         self.config = c
 
     # -- formatted / plain accessors (configuration.py:46-146)
@@ -90,6 +93,7 @@ class Configuration:
     stepGraph = property(lambda s: bool(s.config["stepGraph"]))
     rotateAugmentation = property(lambda s: float(s.config["rotateAugmentation"]))
     residentDataset = property(lambda s: bool(s.config["residentDataset"]))
+    cornerTargets = property(lambda s: bool(s.config["cornerTargets"]))
 
     def useGPU(self):
         # a bound method, hence always truthy when tested without a call (reference quirk)

@@ -7,6 +7,8 @@
 // with g = exp(-(dx^2 + dy^2) / (2 sigma sigma)) in double -- the reference's float64 Gaussian added to the
 // float32 map, rounded back, clipped after every splat -- so overlapping objects clip exactly as there.
 // Grid: B tiles x gridDim.y pixel slices (enough workgroups to fill the chip at B = 32).
+// scd_render_corner_targets (below) renders the two corner maps of CornerNetLoss with the centre map from the same
+// device functions.
 #include <math.h>
 
 #include <algorithm>
@@ -36,6 +38,56 @@ __device__ double center_radius(double width, double height, double thr) {
     return fmin(fmin(r1, r2), r3);
 }
 
+// The splat of one object, from its row: half window `roi` = ceil(2 radius) and the Gaussian's denominator 2 sigma^2,
+// sigma = radius / 3.  The corner maps splat the centre's Gaussian, so this is evaluated once per object.
+__device__ __forceinline__ void splat_shape(const float* o, float thr, int& roi, double& den) {
+    const float major2 = o[4] * o[4] + o[5] * o[5];    // float32, as the dataset computes it
+    const double radius = center_radius(2.0 * sqrt((double)major2), 2.0 * (double)o[6], (double)thr);
+    roi = (int)ceil(radius * 2);
+    const double sigma = radius / 3;
+    den = 2 * sigma * sigma;
+}
+
+// the window of a splat at cell (x, y) inside the map, clipped at the map's border
+__device__ __forceinline__ void splat_window(ObjBox& bx, int x, int y, int roi, double den, int H) {
+    bx.x = x; bx.y = y;
+    bx.l = min(roi, x); bx.r = min(roi, H - x - 1);
+    bx.t = min(roi, y); bx.b = min(roi, H - y - 1);
+    bx.den = den;
+}
+
+// the centre's cell of slot k (int(loc[0]), int(loc[1]): truncation) and whether it lies on the map; slots past the
+// count are outside
+__device__ __forceinline__ int center_cell(const float* o, int k, int cnt, int H, int& x, int& y) {
+    x = (int)o[0]; y = (int)o[1];
+    return (k < cnt && x >= 0 && x < H && y >= 0 && y < H) ? 1 : 0;
+}
+
+// mask / index / regression rows of slot k of tile n (slots past the count stay zero)
+__device__ __forceinline__ void write_rows(const float* o, int n, int k, int K, int cnt, int H, int inside,
+                                           uint8_t* __restrict__ mask, float* __restrict__ regr,
+                                           int64_t* __restrict__ inds) {
+    mask[(size_t)n * K + k] = (uint8_t)inside;
+    inds[(size_t)n * K + k] = inside ? (int64_t)floorf(o[1]) * H + (int64_t)floorf(o[0]) : 0;
+#pragma unroll
+    for (int j = 0; j < 6; ++j) regr[((size_t)n * K + k) * 6 + j] = k < cnt ? o[2 + j] : 0.f;
+}
+
+// pixel (px, py) of a map: the first cnt boxes applied in slot order
+__device__ __forceinline__ float splat_pixel(const ObjBox* box, int cnt, int px, int py) {
+    float h = 0.f;
+    for (int k = 0; k < cnt; ++k) {
+        const ObjBox& bx = box[k];
+        if (!bx.inside) continue;
+        const int dx = px - bx.x, dy = py - bx.y;
+        if (dx < -bx.l || dx > bx.r || dy < -bx.t || dy > bx.b) continue;
+        const double g = exp(-(double)(dx * dx + dy * dy) / bx.den);
+        const float s = (float)(g + (double)h);
+        h = s > 1.f ? 1.f : s;                                // heatmap[heatmap > 1] = 1 (NaN stays NaN)
+    }
+    return h;
+}
+
 __global__ __launch_bounds__(256) void render_center_kernel(const float* __restrict__ locs, const int* __restrict__ counts,
                                                             int K, int H, float thr, float* __restrict__ heat,
                                                             uint8_t* __restrict__ mask, float* __restrict__ regr,
@@ -47,44 +99,75 @@ __global__ __launch_bounds__(256) void render_center_kernel(const float* __restr
     for (int k = threadIdx.x; k < K; k += blockDim.x) {
         const float* o = L + k * 8;
         ObjBox bx;
-        bx.inside = 0;
-        if (k < cnt) {
-            const int x = (int)o[0], y = (int)o[1];               // int(loc[0]), int(loc[1]): truncation
-            bx.x = x; bx.y = y;
-            bx.inside = (x >= 0 && x < H && y >= 0 && y < H) ? 1 : 0;
-            if (bx.inside) {
-                const float major2 = o[4] * o[4] + o[5] * o[5];    // float32, as the dataset computes it
-                const double radius = center_radius(2.0 * sqrt((double)major2), 2.0 * (double)o[6], (double)thr);
-                const int roi = (int)ceil(radius * 2);
-                bx.l = min(roi, x); bx.r = min(roi, H - x - 1);
-                bx.t = min(roi, y); bx.b = min(roi, H - y - 1);
-                const double sigma = radius / 3;
-                bx.den = 2 * sigma * sigma;
-            }
+        int x, y;
+        bx.inside = center_cell(o, k, cnt, H, x, y);
+        if (bx.inside) {
+            int roi;
+            double den;
+            splat_shape(o, thr, roi, den);
+            splat_window(bx, x, y, roi, den, H);
         }
-        if (k < MAXOBJ) box[k] = bx;
-        if (blockIdx.y != 0) continue;
-        // mask / index / regression rows of every slot (slots past the count stay zero)
-        mask[(size_t)n * K + k] = (uint8_t)bx.inside;
-        inds[(size_t)n * K + k] = bx.inside ? (int64_t)floorf(o[1]) * H + (int64_t)floorf(o[0]) : 0;
-#pragma unroll
-        for (int j = 0; j < 6; ++j) regr[((size_t)n * K + k) * 6 + j] = k < cnt ? o[2 + j] : 0.f;
+        box[k] = bx;
+        if (blockIdx.y == 0) write_rows(o, n, k, K, cnt, H, bx.inside, mask, regr, inds);
     }
     __syncthreads();
     float* hm = heat + (size_t)n * H * H;
     for (int p = blockIdx.y * blockDim.x + threadIdx.x; p < H * H; p += gridDim.y * blockDim.x) {
         const int py = p / H, px = p - (p / H) * H;
-        float h = 0.f;
-        for (int k = 0; k < cnt; ++k) {
-            const ObjBox& bx = box[k];
-            if (!bx.inside) continue;
-            const int dx = px - bx.x, dy = py - bx.y;
-            if (dx < -bx.l || dx > bx.r || dy < -bx.t || dy > bx.b) continue;
-            const double g = exp(-(double)(dx * dx + dy * dy) / bx.den);
-            const float s = (float)(g + (double)h);
-            h = s > 1.f ? 1.f : s;                                // heatmap[heatmap > 1] = 1 (NaN stays NaN)
+        hm[p] = splat_pixel(box, cnt, px, py);
+    }
+}
+
+// ---- scd_render_corner_targets: the centre map and the two corner maps of CornerNetLoss in one launch ------------
+// The corner rule is the project's (trainer/dataset/syntheticCorner.py corner_locs; the reference ships no corner
+// encoder): top-left = centre - (d_x, d_y), bottom-right = centre + (d_x, d_y), d_x = round(|majx|), d_y = round(minl)
+// (half to even), each coordinate clipped to [0, H - 1] and truncated to its cell, all in float32; the splat is the
+// centre's (same radius, sigma and window rule).  Completed where the host rule is undefined: a corner is drawn only
+// when the object's centre is on the map and both of the corner's coordinates are finite.
+// Phase 1 decodes three boxes per object into LDS (3 x 64 x 40 B), the radius once per object; phase 2 is the centre
+// kernel's pixel walk, the three maps either looped over by one thread (gridDim.z == 1) or spread over gridDim.z == 3.
+
+// np.clip(v, 0, hi): NaN stays NaN
+__device__ __forceinline__ float clip_coord(float v, float hi) { return v < 0.f ? 0.f : (v > hi ? hi : v); }
+
+__global__ __launch_bounds__(256) void render_corner_kernel(const float* __restrict__ locs, const int* __restrict__ counts,
+                                                            int K, int H, float thr, float* __restrict__ heat,
+                                                            float* __restrict__ tl, float* __restrict__ br,
+                                                            uint8_t* __restrict__ mask, float* __restrict__ regr,
+                                                            int64_t* __restrict__ inds) {
+    __shared__ ObjBox box[3][MAXOBJ];
+    const int n = blockIdx.x;
+    const int cnt = min(counts[n], K);
+    const float* L = locs + (size_t)n * K * 8;
+    for (int k = threadIdx.x; k < K; k += blockDim.x) {
+        const float* o = L + k * 8;
+        ObjBox ct, c0, c1;
+        int x, y;
+        ct.inside = center_cell(o, k, cnt, H, x, y);
+        c0.inside = c1.inside = 0;
+        if (ct.inside) {
+            int roi;
+            double den;
+            splat_shape(o, thr, roi, den);
+            splat_window(ct, x, y, roi, den, H);
+            const float hi = (float)(H - 1);
+            const float dx = rintf(fabsf(o[4])), dy = rintf(o[6]);
+            const float x0 = clip_coord(o[0] - dx, hi), y0 = clip_coord(o[1] - dy, hi);
+            const float x1 = clip_coord(o[0] + dx, hi), y1 = clip_coord(o[1] + dy, hi);
+            // finite after the clip means not NaN, and then inside [0, H - 1]
+            if (x0 == x0 && y0 == y0) { c0.inside = 1; splat_window(c0, (int)x0, (int)y0, roi, den, H); }
+            if (x1 == x1 && y1 == y1) { c1.inside = 1; splat_window(c1, (int)x1, (int)y1, roi, den, H); }
         }
-        hm[p] = h;
+        box[0][k] = ct; box[1][k] = c0; box[2][k] = c1;
+        if (blockIdx.y == 0 && blockIdx.z == 0) write_rows(o, n, k, K, cnt, H, ct.inside, mask, regr, inds);
+    }
+    __syncthreads();
+    for (int m = blockIdx.z; m < 3; m += gridDim.z) {
+        float* hm = (m == 0 ? heat : m == 1 ? tl : br) + (size_t)n * H * H;
+        for (int p = blockIdx.y * blockDim.x + threadIdx.x; p < H * H; p += gridDim.y * blockDim.x) {
+            const int py = p / H, px = p - (p / H) * H;
+            hm[p] = splat_pixel(box[m], cnt, px, py);
+        }
     }
 }
 
@@ -204,4 +287,24 @@ extern "C" int scd_render_center_targets(const float* locs, const int* counts, i
     hipLaunchKernelGGL(render_center_kernel, dim3(B, slices), dim3(256), 0, (hipStream_t)stream, locs, counts, K, H, threshold,
                        heat, mask, regr, inds);
     SCD_RETURN_LAUNCH();
+}
+
+extern "C" int scd_render_corner_targets_split(const float* locs, const int* counts, int B, int K, int H, float threshold,
+                                               float* heat, float* tl, float* br, uint8_t* mask, float* regr,
+                                               int64_t* inds, int split, void* stream) {
+    if (!locs || !counts || !heat || !tl || !br || !mask || !regr || !inds) return SCD_ERR_ARG;
+    if (B < 1 || K < 1 || K > MAXOBJ || H < 1 || (long)H * H >= (1L << 31)) return SCD_ERR_ARG;
+    if (split != SCD_CORNER_SPLIT_THREAD && split != SCD_CORNER_SPLIT_GRID) return SCD_ERR_ARG;
+    const int slices = std::max(1, std::min(64, cdiv((long)H * H, 256)));
+    const int maps = split == SCD_CORNER_SPLIT_GRID ? 3 : 1;
+    hipLaunchKernelGGL(render_corner_kernel, dim3(B, slices, maps), dim3(256), 0, (hipStream_t)stream, locs, counts, K, H,
+                       threshold, heat, tl, br, mask, regr, inds);
+    SCD_RETURN_LAUNCH();
+}
+
+extern "C" int scd_render_corner_targets(const float* locs, const int* counts, int B, int K, int H, float threshold,
+                                         float* heat, float* tl, float* br, uint8_t* mask, float* regr, int64_t* inds,
+                                         void* stream) {
+    return scd_render_corner_targets_split(locs, counts, B, K, H, threshold, heat, tl, br, mask, regr, inds,
+                                           SCD_CORNER_SPLIT_DEFAULT, stream);
 }

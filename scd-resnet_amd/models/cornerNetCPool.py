@@ -125,6 +125,12 @@ class CornerNetLoss(torch.nn.Module):
     def forward(self, outs, targets):
         if self.focal is not focalLoss or len(outs) != 1:
             raise NotImplementedError("fused HIP focal loss over one output stack")
+        t = targets
+        if (len(t) != 5 or not all(torch.is_tensor(t[k]) and t[k].is_floating_point() and t[k].shape == t[0].shape
+                                   for k in (0, 3, 4))):
+            raise RuntimeError("CornerNetLoss needs the corner layout [heat, mask, regr, tl, br] with tl and br float maps "
+                               "of heat's shape, got %d targets: train cornerNetCPool on the `syntheticCorner` dataset "
+                               "or on a `.d` plugin with the configuration key \"cornerTargets\": true" % len(t))
         o = outs[0]
         loss, _ = FocalOnlyLossFn.apply(o["heatmap"], o["tl"], o["br"], targets[0], targets[3], targets[4])
         return loss, {}
@@ -141,9 +147,36 @@ def decodeCornerNet(outputDictionary, K=100, nmsKernelSize=3, **kwargs):
     return res + [outputDictionary]
 
 
+HIT_SCORE = 0.3             # a detection counts from this score on
+HIT_LEVELS = (0.5, 0.75)     # ... and hits when the ground-truth map at its cell reaches these
+
+
 def cornerNetEvaluation(xs, ys, *decoded):
-    """Validation metrics hook (cornerNetCPool.py:308-322): object counts and score statistics
-    (the reference's AP metrics are SURVEY §8f row 3)."""
+    """Validation metrics hook (cornerNetCPool.py:308-322): object counts, score statistics and `hits`, an int64 (3,3)
+    tensor on the maps' device: per map (rows heatmap / tl / br, against ys[0], ys[3], ys[4]) the detections with score
+    >= HIT_SCORE, and those of them whose ground-truth map value at the decoded cell (y, x) is >= 0.5 and >= 0.75.
+    The reference's hook calls an averagePrecision that exists nowhere in it, so these counts are this project's and
+    stand for no reference metric.  Plain torch gathers, no host read."""
     outputDictionary = decoded[-1]
+    hits = []
+    for m, gt in enumerate((ys[0], ys[3], ys[4])):
+        scores, _, cy, cx = decoded[4 * m:4 * m + 4]
+        W = gt.shape[-1]
+        at = gt.reshape(gt.shape[0], -1).gather(1, cy.long() * W + cx.long())
+        det = scores >= HIT_SCORE
+        hits.append(torch.stack([det.sum()] + [(det & (at >= lv)).sum() for lv in HIT_LEVELS]))
     return {"objs": [int(m.sum().item()) for m in ys[1]], "scores": decoded[0].detach(),
-            "valid": (decoded[0] >= 0.3).detach()}, outputDictionary
+            "valid": (decoded[0] >= 0.3).detach(), "hits": torch.stack(hits).detach()}, outputDictionary
+
+
+def expression(batches):
+    """The evals line of a validation pass: objs and hits summed over the batches, read once.  Per map the detections
+    (score >= 0.3) and the share of them on a ground-truth value >= 0.5 and >= 0.75 (0 without detections)."""
+    objNum = sum(int(sum(b['objs'])) for b in batches)
+    hits = torch.stack([b['hits'] for b in batches]).sum(0).tolist() if batches else [[0] * 3] * 3
+    parts = ["[Obj] {}".format(format(objNum, '-7d'))]
+    for name, (det, h50, h75) in zip(("Ct", "TL", "BR"), hits):
+        parts.append("[{}] {}    [{}hit50] {}    [{}hit75] {}".format(
+            name, format(det, '-7d'), name, format(100.0 * h50 / det if det else 0.0, '-5.2f'),
+            name, format(100.0 * h75 / det if det else 0.0, '-5.2f')))
+    return "    ".join(parts)

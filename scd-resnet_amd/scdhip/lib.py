@@ -138,6 +138,8 @@ SIGNATURES = {
     "scd_adam_step_dev": (I, [P, P, P, P, L, P, F, F, F, F, P, P]),
     "scd_sgd_step_dev": (I, [P, P, P, L, P, F, F, F, I, F, P, P]),
     "scd_render_center_targets": (I, [P, P, I, I, I, F, P, P, P, P, P]),
+    "scd_render_corner_targets": (I, [P, P, I, I, I, F, P, P, P, P, P, P, P]),
+    "scd_render_corner_targets_split": (I, [P, P, I, I, I, F, P, P, P, P, P, P, I, P]),
     "scd_cpool_fwd": (I, [I, I, P, P, P, I, I, I, I, P]),
     "scd_cpool_bwd": (I, [I, I, P, P, P, I, I, I, I, P]),
     "scd_nms": (I, [P, L, I, I, I, P, P]),

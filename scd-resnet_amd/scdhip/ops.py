@@ -1599,6 +1599,33 @@ def render_center_targets(locs, counts, size=128, threshold=0.5):
     return [heat, mask, regr, inds]
 
 
+CORNER_SPLITS = {"thread": 0, "grid": 1}      # SCD_CORNER_SPLIT_*: who renders a pixel's three maps
+
+
+def render_corner_targets(locs, counts, size=128, threshold=0.5, split=None):
+    """CornerNet targets on the GPU (scd_render_corner_targets, one launch): locs (B,K,8) fp32 object rows, counts (B,)
+    objects per tile -> [heat, mask, regr, tl (B,1,size,size) f32, br, inds]; heat / mask / regr / inds are
+    render_center_targets' bit for bit, the first five entries are CornerNetLoss' target layout.  split: a
+    CORNER_SPLITS key, for tools/corner_targets_bench.py (None: the library's default; every split gives the same
+    bits)."""
+    _need_gpu(locs)
+    locs = locs.float().contiguous()
+    counts = counts.to(device=locs.device, dtype=torch.int32).contiguous()
+    B, K, _ = locs.shape
+    dev = locs.device
+    heat, tl, br = (torch.empty(B, 1, size, size, device=dev) for _ in range(3))
+    mask = torch.empty(B, K, dtype=torch.bool, device=dev)
+    regr = torch.empty(B, K, 6, device=dev)
+    inds = torch.empty(B, K, dtype=torch.int64, device=dev)
+    args = (ptr(locs), ptr(counts), B, K, size, float(threshold), ptr(heat), ptr(tl), ptr(br), ptr(mask), ptr(regr),
+            ptr(inds))
+    if split is None:
+        L.call("scd_render_corner_targets", *args, stream())
+    else:
+        L.call("scd_render_corner_targets_split", *args, CORNER_SPLITS[split], stream())
+    return [heat, mask, regr, tl, br, inds]
+
+
 
 CEVAL_STREAMS = ("iou", "score", "ortho", "ioucenter", "iouoffsetwo", "iouoffset", "aemaj", "aemin", "aerad")
 _CEVAL_STREAM_MASK = (0, 0, 1, 2, 3, 4, 1, 1, 1)

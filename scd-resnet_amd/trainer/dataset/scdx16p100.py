@@ -36,6 +36,10 @@ one store, labels as CSR) and every batch is built there from the same host draw
 scd_rotate_tiles, scd_pack_locs (the flips, the rotation and the packing of the labels in one launch) and
 scd_render_center_targets, without reading a host tile or label.  With the key off, the default,
 nothing of this runs.
+With the configuration key cornerTargets on, training batches (host and resident path) and validation slices carry
+CornerNet's layout ys = [heat, mask, regr, tl, br]: scd_render_corner_targets renders the three maps from the same
+packed rows in one launch, after the flips and the rotation; with the key off, the default, every route
+is what it was.
 """
 import io
 import json
@@ -133,6 +137,16 @@ def _pack_locs(bounds_list, trunc):
     return locs, counts
 
 
+def _render_targets(locs, counts):
+    """The targets of packed device rows: scd_render_center_targets' [heat, mask, regr, inds], or with the configuration
+    key cornerTargets on scd_render_corner_targets' [heat, mask, regr, tl, br, inds] (the first four bit for bit the
+    same)."""
+    from configuration import defaultConfig
+    from scdhip import ops
+    render = ops.render_corner_targets if defaultConfig.cornerTargets else ops.render_center_targets
+    return render(locs, counts, HEATMAPSIZE, THRESHOLDIOU)
+
+
 def splitOrder(count, dataSplit=None, ratio=ARGUMENTRATIO, partition=PARTITION, subset=TRAINSUBSET):
     """Training order and split profile (scdx16p100.py:143-180): FSI x ARGUM x CLIP positions (only the first
     `count` of a smaller test archive) kept when argum < ratio, shuffled with Python's global `random`, cut to
@@ -182,9 +196,10 @@ class SCD(Dataset):
 
     # ------------------------------------------------------------------ validation (scdx16p100.py:185-262)
     def _buildValidation(self, chunk=256):
+        from configuration import defaultConfig
         from scdhip import ops
         ids = self.dataProfile['validation'][:REALTIMETEST]
-        xs, heat, mask, regr, locs, inds = [], [], [], [], [], []
+        xs, heat, mask, regr, locs, inds, tl, br = [], [], [], [], [], [], [], []
         self.validObjNum = [int(len(self.bounds[i])) for i in ids]
         for c0 in range(0, len(ids), chunk):
             part = ids[c0:c0 + chunk]
@@ -192,8 +207,9 @@ class SCD(Dataset):
             xs.append(ops.augment_tiles(tiles))
             l, n = _pack_locs([self.bounds[i] for i in part], trunc=True)
             L = torch.from_numpy(l).to(self.device)
-            h, m, r, ind = ops.render_center_targets(L, torch.from_numpy(n).to(self.device), HEATMAPSIZE,
-                                                     THRESHOLDIOU)
+            h, m, r, *corners, ind = _render_targets(L, torch.from_numpy(n).to(self.device))
+            for kept, c in zip((tl, br), corners):      # cornerTargets on
+                kept.append(c)
             # validation masks every stored object (scdx16p100.py:219-220)
             m = torch.arange(MAXTAGLEN, device=self.device)[None, :] < torch.from_numpy(n).to(self.device)[:, None]
             heat.append(h); mask.append(m); regr.append(r); locs.append(L); inds.append(ind)
@@ -202,25 +218,34 @@ class SCD(Dataset):
             "xs": [cat(xs, (0, 1, 1, 1)), cat(inds, (0, MAXTAGLEN)).long()],
             "ys": [cat(heat, (0, 1, HEATMAPSIZE, HEATMAPSIZE)), cat(mask, (0, MAXTAGLEN)).bool(),
                    cat(regr, (0, MAXTAGLEN, 6)), cat(locs, (0, MAXTAGLEN, 8)), self.validObjNum]}
+        if defaultConfig.cornerTargets:
+            self.validation["corners"] = [cat(t, (0, 1, HEATMAPSIZE, HEATMAPSIZE)) for t in (tl, br)]
 
     def getValidationSet(self):
         """scdx16p100.py:381-414 (REALTIMETEST positions in validationBatchSize slices; empty slices of a small
-        archive are dropped)."""
+        archive are dropped).  With the configuration key cornerTargets on every slice carries CornerNet's layout
+        ys = [heat, mask, regr, tl, br], the corner maps _buildValidation kept."""
         from configuration import defaultConfig
         v = self.validation
         length = REALTIMETEST
         size = defaultConfig.validationBatchSize
+        if defaultConfig.cornerTargets:
+            if "corners" not in v:
+                raise RuntimeError("scdx16p100: cornerTargets was off when this dataset was built, its validation set "
+                                   "holds no corner maps")
+            part = (lambda s: [v['ys'][0][s], v['ys'][1][s], v['ys'][2][s], v['corners'][0][s], v['corners'][1][s]])
+        else:
+            part = (lambda s: [v['ys'][0][s], v['ys'][1][s], v['ys'][2][s], v['ys'][3][s], v['ys'][4][s],
+                               v['xs'][1][s]])
         if length > size:
             out = []
             for k in range(length // size):
                 s = slice(int(k * size), int((k + 1) * size))
                 if len(v['ys'][4][s]) == 0:
                     continue
-                out.append({'xs': [v['xs'][0][s]],
-                            'ys': [v['ys'][0][s], v['ys'][1][s], v['ys'][2][s], v['ys'][3][s], v['ys'][4][s],
-                                   v['xs'][1][s]]})
+                out.append({'xs': [v['xs'][0][s]], 'ys': part(s)})
             return out
-        return [{'xs': [v['xs'][0]], 'ys': [v['ys'][0], v['ys'][1], v['ys'][2], v['ys'][3], v['ys'][4], v['xs'][1]]}]
+        return [{'xs': [v['xs'][0]], 'ys': part(slice(None))}]
 
     # ------------------------------------------------------------------ training samples (scdx16p100.py:300-379)
     def __len__(self):
@@ -296,7 +321,8 @@ class SCD(Dataset):
         """A training batch augmented and target-rendered on the GPU in two launches each (scd_augment_tiles,
         scd_render_center_targets): {"xs": [(B,1,S,S)], "ys": [heat, mask, regr, inds]} on the device, the
         reference's __getitem__ stacked over `indices` (positions in the shuffled order).  With the configuration's
-        rotateAugmentation > 0, scd_rotate_tiles and rotateLocs follow the augmentation and the flips."""
+        rotateAugmentation > 0, scd_rotate_tiles and rotateLocs follow the augmentation and the flips.  With its
+        cornerTargets on, ys = [heat, mask, regr, tl, br] from scd_render_corner_targets on the same rows."""
         from configuration import defaultConfig
         from scdhip import ops
         dev = device or self.device
@@ -315,9 +341,8 @@ class SCD(Dataset):
             xs = ops.rotate_tiles(xs, angles)
             rows = [self.rotateLocs(r, a) for r, a in zip(rows, angles)]
         l, n = _pack_locs(rows, trunc=True)
-        ys = ops.render_center_targets(torch.from_numpy(l).to(dev), torch.from_numpy(n).to(dev), HEATMAPSIZE,
-                                       THRESHOLDIOU)
-        return {"xs": [xs], "ys": ys}
+        ys = _render_targets(torch.from_numpy(l).to(dev), torch.from_numpy(n).to(dev))
+        return {"xs": [xs], "ys": ys[:5]}
 
     # ------------------------------------------------------------------ device-resident archive
     def _buildResident(self, dev, chunk=256):
@@ -351,7 +376,8 @@ class SCD(Dataset):
     def _resident_batch(self, indices, dev):
         """gpu_batch from the device-resident archive: the same draws in the same order, one upload of the batch's
         ids, flips, jitter factors and rotation coefficients, then scd_augment_tiles_indexed, scd_rotate_tiles (when
-        rotateAugmentation > 0), scd_pack_locs and scd_render_center_targets.  No host tile or label is read and
+        rotateAugmentation > 0), scd_pack_locs and scd_render_center_targets (scd_render_corner_targets on the same
+        device rows when cornerTargets is on).  No host tile or label is read and
         there is no explicit synchronise (the one upload, from pageable memory, is a blocking copy on the current
         stream, as every upload of the host path is)."""
         from scdhip import ops
@@ -389,8 +415,7 @@ class SCD(Dataset):
             cs = views[1].view(torch.float32).view(B, 2)
         locs, counts = ops.pack_locs(res["rows"], res["offsets"], dids, dflips, size=HEATMAPSIZE, K=MAXTAGLEN,
                                      trunc=True, cs=cs)
-        ys = ops.render_center_targets(locs, counts, HEATMAPSIZE, THRESHOLDIOU)
-        return {"xs": [xs], "ys": ys}
+        return {"xs": [xs], "ys": _render_targets(locs, counts)[:5]}
 
     def __getitem__(self, index):
         b = self.gpu_batch([index])

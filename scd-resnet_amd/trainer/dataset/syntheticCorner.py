@@ -6,6 +6,8 @@ centre -/+ (round |major_x|, round minor) clipped to the map, rendered with the 
 rule as the centre (tests/golden/make_golden_corner.py:corner_targets builds F8 the same way).
 
   __getitem__ -> {"xs": [tile (1,512,512) f32], "ys": [heat, mask (30,), regr (30,6), tl, br]}
+  gpu_batch(indices, device) -> the same stacked, the three maps rendered on the GPU in one launch
+                                (scd_render_corner_targets); the training loop's route
 """
 import numpy as np
 import torch
@@ -30,6 +32,16 @@ class CornerSCD(SCD):
         tl, br = corner_locs(locs, self.heat)
         return tile, locs, ys[:3] + [torch.from_numpy(encode_targets(tl, self.heat)[0]),
                                      torch.from_numpy(encode_targets(br, self.heat)[0])]
+
+    def gpu_batch(self, indices, device):
+        """SCD.gpu_batch with the corner layout: the same tiles, the three maps from one launch of
+        scd_render_corner_targets -> {"xs": [(B,1,S,S)], "ys": [heat, mask, regr, tl, br]} on `device`, equal to
+        stacking __getitem__(i) for i in indices (tests/test_corner_targets_gpu.py)."""
+        from scdhip import ops
+        from trainer.dataset.syntheticSCD import THRESHOLDIOU
+        tiles, locs, counts = self.batch_rows(indices)
+        ys = ops.render_corner_targets(locs.to(device), counts.to(device), self.heat, THRESHOLDIOU)
+        return {"xs": [tiles.to(device)], "ys": ys[:5]}
 
     def getValidationSet(self, batch=None):
         from configuration import defaultConfig

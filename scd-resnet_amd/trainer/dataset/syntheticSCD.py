@@ -99,11 +99,9 @@ class SCD(Dataset):
         tile, _, ys = self.item(index, self.seed)
         return {"xs": [tile], "ys": ys}
 
-    def gpu_batch(self, indices, device):
-        """A training batch with its targets rendered on the GPU (scdhip.ops.render_center_targets, one launch
-        for the whole batch) instead of per sample on the host: {"xs": [(B,1,S,S)], "ys": [heat, mask, regr,
-        inds]} on `device`, equal to stacking __getitem__(i) for i in indices (tests/test_targets_gpu.py)."""
-        from scdhip import ops
+    def batch_rows(self, indices):
+        """The tiles (B,1,S,S) and the packed object rows (B,MAXTAGLEN,8) with their counts (B,) of the items
+        `indices`, on the host: what gpu_batch uploads."""
         tiles, locs = [], np.zeros((len(indices), MAXTAGLEN, 8), dtype=np.float32)
         counts = np.zeros(len(indices), dtype=np.int32)
         for b, i in enumerate(indices):
@@ -113,9 +111,16 @@ class SCD(Dataset):
             n = min(len(objs), MAXTAGLEN)
             locs[b, :n] = objs[:n]
             counts[b] = n
-        ys = ops.render_center_targets(torch.from_numpy(locs).to(device), torch.from_numpy(counts).to(device),
-                                       self.heat, THRESHOLDIOU)
-        return {"xs": [torch.stack(tiles).to(device)], "ys": ys}
+        return torch.stack(tiles), torch.from_numpy(locs), torch.from_numpy(counts)
+
+    def gpu_batch(self, indices, device):
+        """A training batch with its targets rendered on the GPU (scdhip.ops.render_center_targets, one launch
+        for the whole batch) instead of per sample on the host: {"xs": [(B,1,S,S)], "ys": [heat, mask, regr,
+        inds]} on `device`, equal to stacking __getitem__(i) for i in indices (tests/test_targets_gpu.py)."""
+        from scdhip import ops
+        tiles, locs, counts = self.batch_rows(indices)
+        ys = ops.render_center_targets(locs.to(device), counts.to(device), self.heat, THRESHOLDIOU)
+        return {"xs": [tiles.to(device)], "ys": ys}
 
     def getValidationSet(self, batch=None):
         from configuration import defaultConfig
