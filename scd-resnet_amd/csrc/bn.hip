@@ -199,7 +199,7 @@ __global__ __launch_bounds__(256, BN_EW_WAVES) void bn_bwd_reduce_kernel(const T
         red[nt * E + rsub * C + ch * E + e] = q[e];
     }
     __syncthreads();
-    const int rep = (int)(blockIdx.x % SCD_STAT_REPLICAS);
+    const int rep = (int)(blockIdx.x % SCD_STAT_REPLICAS);   // (mirrors stat_replica / stat_slot, gemm_common.h)
     for (int c = tid; c < C; c += nt) {
         double ss = 0.0, qq = 0.0;
         for (int k = 0; k < rpi; ++k) {
@@ -351,7 +351,7 @@ __global__ __launch_bounds__(256, BN_EW_WAVES) void bn_bwd_reduce2_kernel(const 
         const unsigned i = r * (unsigned)ld + ch * E;
         acc_raw(*(const uint4*)(dout + i), *(const uint4*)(mask + i), *(const uint4*)(ya + i), *(const uint4*)(yb + i));
     }
-    const int rep = (int)(blockIdx.x % SCD_STAT_REPLICAS);
+    const int rep = (int)(blockIdx.x % SCD_STAT_REPLICAS);   // (mirrors stat_replica / stat_slot, gemm_common.h)
     // pass 1: sum dz (both layers) and layer a's sum dz*xhat; pass 2: layer b's
 #pragma unroll
     for (int e = 0; e < E; ++e) {

@@ -94,9 +94,52 @@ struct GemmParams {
         }                                                                             \
     }
 
-// LDS image of one operand stage: rows of 128 B (BK elements), 16-B chunk c of row r stored at
-// chunk c ^ (r & 7).  ds_read_b128 fragment reads (16 consecutive rows, one chunk) and the
-// ds_write_b128 staging stores (8 chunks of one row) are then bank-conflict free.
+// XCD-aware bijective remap of the 1-D grid (workgroups go to the 8 XCDs round-robin on blockIdx): consecutive tile
+// ids run on one XCD, so the tiles that share an A (pixel) panel share its L2
+__device__ __forceinline__ int xcd_tile_id() {
+    const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = blockIdx.x & 7;
+    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (blockIdx.x >> 3);
+}
+
+// Tile id -> the launch's tile table (fill_tiles): the phase whose range holds it, the pixel tile mt and the column
+// tile nt inside the phase, the phase's pixels per image QQ and GEMM rows M
+struct GemmTile { int phase, mt, nt, QQ, M; };
+__device__ __forceinline__ GemmTile gemm_tile(const GemmParams& p, int bid) {
+    GemmTile t;
+    t.phase = 0;
+#pragma unroll
+    for (int i = 1; i < SCD_MAX_PHASES; ++i)
+        if (i < p.nphase && bid >= p.tile_start[i]) t.phase = i;
+    const scd_gemm_phase& ph = p.ph[t.phase];
+    const int local = bid - p.tile_start[t.phase];
+    t.mt = local / p.ntn;
+    t.nt = local - t.mt * p.ntn;
+    t.QQ = ph.Qh * ph.Qw;
+    t.M = p.N * t.QQ;
+    return t;
+}
+
+// The barrier of the hand-scheduled loops: raw (a __syncthreads() fence would drain the DMA stages in flight), and
+// fenced so the compiler moves nothing across it.  ON = false: the no-barrier ablation build
+template <bool ON = true>
+__device__ __forceinline__ void pp_barrier() {
+    __builtin_amdgcn_sched_barrier(0);
+    if constexpr (ON) __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_sched_barrier(0);
+}
+
+// GEMM row m of a phase -> image n and position (qh, qw) on the phase's Qh x Qw grid
+struct PixPos { int n, qh, qw; };
+__device__ __forceinline__ PixPos pix_of(int m, int QQ, int Qw) {
+    PixPos q;
+    q.n = m / QQ;
+    const int rem = m - q.n * QQ;
+    q.qh = rem / Qw;
+    q.qw = rem - q.qh * Qw;
+    return q;
+}
+
+// (LDS image of one operand stage: swz, gemm_common.h)
 // 16x16x16 MFMA on 4-element 16-bit vectors (the 16-bit type is h16, or _Float16 in the SCD_F16_BUILD pass)
 typedef __attribute__((ext_vector_type(4))) h16 hx4;
 __device__ __forceinline__ f32x4 mfma_16x16x16(hx4 a, hx4 b, f32x4 c) {
@@ -110,17 +153,6 @@ __device__ __forceinline__ f32x4 mfma_16x16x16(hx4 a, hx4 b, f32x4 c) {
 // (The ping-pong kernels -- conv_gemm_pp, heads384, wgrad_pp2 -- set s_setprio 1 around every MFMA segment, the round-1
 // form; a static priority for the second-dispatched group for the whole main loop, MI355X_MICROARCH.md "Two waves per
 // SIMD" item 4, and none at all were A/B builds that did not replace it.)
-
-// sum over the 16 lanes of a DPP row (every lane gets it): quad butterflies, then the half-row and row mirrors
-__device__ __forceinline__ float row16_sum(float v) {
-    v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x141, 0xF, 0xF, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x140, 0xF, 0xF, true));
-    return v;
-}
-
-__device__ __forceinline__ int swz(int row, int chunk) { return row * 128 + ((chunk ^ (row & 7)) << 4); }
 
 // Buffer-load offset or an out-of-range one (the load then returns zeros).  The offset is made
 // opaque before the select so the compiler cannot sink its arithmetic into an exec-masked branch:
@@ -166,10 +198,8 @@ __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, f32x4 (&acc)[
 #pragma unroll
         for (int a = 0; a < 4; ++a) {
             const int m = mt * BM + wm * 64 + a * 16 + l16;
-            const int n = m / QQ;
-            const int rem = m - n * QQ;
-            const int qh = rem / ph.Qw, qw = rem - (rem / ph.Qw) * ph.Qw;
-            pix[a] = m < M ? (n * p.Ho + p.os * qh + ph.rho_h) * p.Wo + p.os * qw + ph.rho_w : -1;
+            const PixPos q = pix_of(m, QQ, ph.Qw);
+            pix[a] = m < M ? (q.n * p.Ho + p.os * q.qh + ph.rho_h) * p.Wo + p.os * q.qw + ph.rho_w : -1;
         }
     }
 #pragma unroll
@@ -298,7 +328,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, f32x4 (&acc)[
                 if (!ok) continue;
             }
             const int m = SELF ? (ok ? mr : 0) : mr;
-            const int n = m / QQ;
+            const int n = m / QQ;                          // (mirrors pix_of)
             const int rem = m - n * QQ;
             const int qh = rem / ph.Qw;
             const int qw = rem - qh * ph.Qw;
@@ -337,7 +367,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, f32x4 (&acc)[
                 double s = 0.0, q = 0.0;
 #pragma unroll
                 for (int w = 0; w < BM / 64; ++w) { s += red[(w * BN + tid) * 2]; q += red[(w * BN + tid) * 2 + 1]; }
-                const int rep = bid % SCD_STAT_REPLICAS;
+                const int rep = bid % SCD_STAT_REPLICAS;    // (mirrors stat_replica / stat_slot, gemm_common.h)
                 atomic_add_f64(p.stats + ((long)rep * 2 + 0) * p.Co + col, s);
                 atomic_add_f64(p.stats + ((long)rep * 2 + 1) * p.Co + col, q);
             }
@@ -371,13 +401,10 @@ __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, f32x4 (&acc)[
             for (int o = 0; o < 4; ++o) o4[o] += __shfl_xor(o4[o], 1, 64);
             const int m = mt * BM + row;
             if (half == 0 && m < M) {
-                const int n = m / QQ;
-                const int rem = m - n * QQ;
-                const int qh = rem / ph.Qw;
-                const int qw = rem - qh * ph.Qw;
-                const int oh = p.os * qh + ph.rho_h, ow = p.os * qw + ph.rho_w;
+                const PixPos q = pix_of(m, QQ, ph.Qw);
+                const int oh = p.os * q.qh + ph.rho_h, ow = p.os * q.qw + ph.rho_w;
                 for (int o = 0; o < od; ++o)
-                    p.head_out[h][((long)n * od + o) * p.Ho * p.Wo + oh * p.Wo + ow] = o4[o] + p.head_b[h][o];
+                    p.head_out[h][((long)q.n * od + o) * p.Ho * p.Wo + oh * p.Wo + ow] = o4[o] + p.head_b[h][o];
             }
         }
     }
@@ -406,22 +433,10 @@ __global__ __launch_bounds__(256 * KS, 2 / KS) void conv_gemm_kernel(GemmParams 
     const int grp = KS == 1 ? 0 : (int)(threadIdx.x >> 8);
     const int tid = threadIdx.x & 255;
     char* const gsm = smem + grp * 2 * STAGE;     // this group's two operand stages
-    // XCD-aware bijective remap: blocks that share an A (pixel) tile run on one XCD's L2
-    int bid;
-    {
-        const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = blockIdx.x & 7;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (blockIdx.x >> 3);
-    }
-    int phase = 0;
-#pragma unroll
-    for (int i = 1; i < SCD_MAX_PHASES; ++i)
-        if (i < p.nphase && bid >= p.tile_start[i]) phase = i;
-    const scd_gemm_phase& ph = p.ph[phase];
-    const int local = bid - p.tile_start[phase];
-    const int mt = local / p.ntn;
-    const int nt = local - mt * p.ntn;
-    const int QQ = ph.Qh * ph.Qw;
-    const int M = p.N * QQ;
+    const int bid = xcd_tile_id();
+    const GemmTile tile = gemm_tile(p, bid);
+    const scd_gemm_phase& ph = p.ph[tile.phase];
+    const int mt = tile.mt, nt = tile.nt, QQ = tile.QQ, M = tile.M;
 
     // ---- per-thread gather rows (fixed across the K loop)
     const int cch = tid & 7;
@@ -432,14 +447,10 @@ __global__ __launch_bounds__(256 * KS, 2 / KS) void conv_gemm_kernel(GemmParams 
     for (int i = 0; i < ACH; ++i) {
         int m = mt * BM + srow + 32 * i;
         a_ok[i] = m < M;
-        int mm = a_ok[i] ? m : 0;
-        int n = mm / QQ;
-        int rem = mm - n * QQ;
-        int qh = rem / ph.Qw;
-        int qw = rem - qh * ph.Qw;
-        a_pix[i] = n * p.Hi * p.Wi;
-        a_ih[i] = p.is * qh;
-        a_iw[i] = p.is * qw;
+        const PixPos q = pix_of(a_ok[i] ? m : 0, QQ, ph.Qw);
+        a_pix[i] = q.n * p.Hi * p.Wi;
+        a_ih[i] = p.is * q.qh;
+        a_iw[i] = p.is * q.qw;
     }
     int b_row[BCH];
     bool b_ok[BCH];
@@ -458,8 +469,8 @@ __global__ __launch_bounds__(256 * KS, 2 / KS) void conv_gemm_kernel(GemmParams 
 
     // raw buffer loads: out-of-range lanes use an offset past num_records and read zeros
     // (no exec-mask branches around the loads, so the compiler can count vmcnt per stage)
-    const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, (short)0, p.xbytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, (short)0, p.wbytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t xrs = buf_rsrc(p.x, p.xbytes);
+    const __amdgpu_buffer_rsrc_t wrs = buf_rsrc(p.w, p.wbytes);
     auto gload = [&](int kt_req, uint4 (&ra)[ACH], uint4 (&rb)[BCH]) {
         // stages past the end are issued with out-of-range offsets (no traffic, no branch)
         const bool live = kb + kt_req < ke;
@@ -674,8 +685,8 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_l1p_kernel(GemmParams p, int
     const int t0 = blockIdx.x * run;
     const int n = t0 / tpi, r0 = (t0 - n * tpi) * TR;
 
-    const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, (short)0, p.xbytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, (short)0, p.wbytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t xrs = buf_rsrc(p.x, p.xbytes);
+    const __amdgpu_buffer_rsrc_t wrs = buf_rsrc(p.w, p.wbytes);
 
     // ---- input rows -> ring slot (row + 1) % RING; one 1-KB DMA per 8 pixel slots (lane: slot lane/8, chunk lane%8)
     const int hq = lane >> 3, csrc = (lane & 7) ^ hq;
@@ -731,7 +742,7 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_l1p_kernel(GemmParams p, int
         for (int b = 0; b < 2; ++b)
 #pragma unroll
             for (int q = 0; q < 4; ++q) bz[b][q] = p.bias ? p.bias[32 * chh + 16 * b + 4 * lg + q] : 0.f;
-        rrs = __builtin_amdgcn_make_buffer_rsrc((void*)(p.res ? p.res : p.x), (short)0, p.res ? p.ybytes : 0, 0x00020000);
+        rrs = buf_rsrc(p.res ? p.res : p.x, p.res ? p.ybytes : 0);
     }
     const int cc = tid & 7;                       // store phase: this thread's 8-channel chunk
 
@@ -924,8 +935,8 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_l1p_kernel(GemmParams p, int
 
     // ---- BN sums: once per workgroup into replica blockIdx % SCD_STAT_REPLICAS
     if ((BNB || p.stats) && tid < 128) {
-        const int rep = blockIdx.x % SCD_STAT_REPLICAS;
-        atomic_add_f64(p.stats + ((long)rep * 2 + (tid >> 6)) * p.Co + (tid & 63), (double)bnsum);
+        const int rep = stat_replica(blockIdx.x);
+        atomic_add_f64(stat_slot(p.stats, rep, tid >> 6, p.Co, tid & 63), (double)bnsum);
     }
 }
 
@@ -940,21 +951,10 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_ring_kernel(GemmParams p) {
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    int bid;
-    {
-        const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = blockIdx.x & 7;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (blockIdx.x >> 3);
-    }
-    int phase = 0;
-#pragma unroll
-    for (int i = 1; i < SCD_MAX_PHASES; ++i)
-        if (i < p.nphase && bid >= p.tile_start[i]) phase = i;
-    const scd_gemm_phase& ph = p.ph[phase];
-    const int local = bid - p.tile_start[phase];
-    const int mt = local / p.ntn;
-    const int nt = local - mt * p.ntn;
-    const int QQ = ph.Qh * ph.Qw;
-    const int M = p.N * QQ;
+    const int bid = xcd_tile_id();
+    const GemmTile tile = gemm_tile(p, bid);
+    const scd_gemm_phase& ph = p.ph[tile.phase];
+    const int mt = tile.mt, nt = tile.nt, QQ = tile.QQ, M = tile.M;
 
     // DMA rows of this lane: A rows 32*wave + 8*i + lane/8 (i < 4), B rows 16*wave + 8*j + lane/8 (j < 2);
     // the lane fetches logical chunk (lane & 7) ^ (row & 7) so that LDS slot (lane & 7) holds it.
@@ -966,14 +966,10 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_ring_kernel(GemmParams p) {
     for (int i = 0; i < 4; ++i) {
         const int m = mt * BM + 32 * wave + 8 * i + lrow;
         a_ok[i] = m < M;
-        const int mm = a_ok[i] ? m : 0;
-        const int n = mm / QQ;
-        const int rem = mm - n * QQ;
-        const int qh = rem / ph.Qw;
-        const int qw = rem - qh * ph.Qw;
-        a_pix[i] = n * p.Hi * p.Wi;
-        a_ih[i] = p.is * qh;
-        a_iw[i] = p.is * qw;
+        const PixPos q = pix_of(a_ok[i] ? m : 0, QQ, ph.Qw);
+        a_pix[i] = q.n * p.Hi * p.Wi;
+        a_ih[i] = p.is * q.qh;
+        a_iw[i] = p.is * q.qw;
     }
     int b_row[2];
     bool b_ok[2];
@@ -985,8 +981,8 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_ring_kernel(GemmParams p) {
     }
     const int cpt = p.Ci / BK;
     const int KT = ph.ntaps * cpt;
-    const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, (short)0, p.xbytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, (short)0, p.wbytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t xrs = buf_rsrc(p.x, p.xbytes);
+    const __amdgpu_buffer_rsrc_t wrs = buf_rsrc(p.w, p.wbytes);
 
     // per-stage tap parameters (scalar loads from the phase table), fetched one step ahead so their
     // latency is not exposed after the barrier
@@ -1103,21 +1099,10 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_pp_kernel(GemmParams p) {
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int grp = wave >> 2, wc = wave & 3;
-    int bid;
-    {
-        const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = blockIdx.x & 7;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (blockIdx.x >> 3);
-    }
-    int phase = 0;
-#pragma unroll
-    for (int i = 1; i < SCD_MAX_PHASES; ++i)
-        if (i < p.nphase && bid >= p.tile_start[i]) phase = i;
-    const scd_gemm_phase& ph = p.ph[phase];
-    const int local = bid - p.tile_start[phase];
-    const int mt = local / p.ntn;
-    const int nt = local - mt * p.ntn;
-    const int QQ = ph.Qh * ph.Qw;
-    const int M = p.N * QQ;
+    const int bid = xcd_tile_id();
+    const GemmTile tile = gemm_tile(p, bid);
+    const scd_gemm_phase& ph = p.ph[tile.phase];
+    const int mt = tile.mt, nt = tile.nt, QQ = tile.QQ, M = tile.M;
 
     // DMA rows of this lane (the lane fetches chunk (lane&7)^(row&7) so that LDS slot lane&7 holds it)
     const int lrow = lane >> 3;
@@ -1132,14 +1117,10 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_pp_kernel(GemmParams p) {
     for (int i = 0; i < 4; ++i) {
         const int m = mt * BM + 128 * grp + 64 * (i >> 1) + 16 * wc + 8 * (i & 1) + lrow;
         const bool ok = m < M;
-        const int mm = ok ? m : 0;
-        const int n = mm / QQ;
-        const int rem = mm - n * QQ;
-        const int qh = rem / ph.Qw;
-        const int qw = rem - qh * ph.Qw;
-        const int ih0 = p.is * qh, iw0 = p.is * qw;
-        a_base[i] = ((n * p.Hi + ih0) * p.Wi + iw0) * p.Ci * 2 + cch * EPC * 2;
-        unsigned msk = 0;
+        const PixPos q = pix_of(ok ? m : 0, QQ, ph.Qw);
+        const int ih0 = p.is * q.qh, iw0 = p.is * q.qw;
+        a_base[i] = ((q.n * p.Hi + ih0) * p.Wi + iw0) * p.Ci * 2 + cch * EPC * 2;
+        unsigned msk = 0;                                  // (conv_gemm_heads384_kernel mirrors this loop)
         for (int t = 0; t < ph.ntaps; ++t) {
             const int ih = ih0 + ph.dh[t], iw = iw0 + ph.dw[t];
             if (ok && (unsigned)ih < (unsigned)p.Hi && (unsigned)iw < (unsigned)p.Wi) msk |= 1u << t;
@@ -1158,9 +1139,11 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_pp_kernel(GemmParams p) {
     }
     const int cpt = p.Ci / BK;
     const int KT = ph.ntaps * cpt;
-    const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, (short)0, p.xbytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, (short)0, p.wbytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t xrs = buf_rsrc(p.x, p.xbytes);
+    const __amdgpu_buffer_rsrc_t wrs = buf_rsrc(p.w, p.wbytes);
 
+    // (conv_gemm_heads384_kernel's stage_args is this one plus the reversed K order; one shared function changed both
+    // kernels' code, so each keeps its copy)
     struct StageArgs { int live, tap, adelta, bdelta; };
     auto stage_args = [&](int kt_req) {
         StageArgs a;
@@ -1244,11 +1227,7 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_pp_kernel(GemmParams p) {
     // 5 = no barriers in the loop, 60 = no output stores, 61 = no epilogue (timing only; 3-5, 60, 61 give wrong
     // results; tools/pp_probe.py)
     constexpr int dbg = SCD_ABLATE;
-    auto bar = [&]() {
-        __builtin_amdgcn_sched_barrier(0);
-        if constexpr (dbg != 5) __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-    };
+    auto bar = [&]() { pp_barrier<dbg != 5>(); };
 
     SCD_STAMP_BEGIN();
     if (KT > 0) {
@@ -1324,15 +1303,6 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_pp_kernel(GemmParams p) {
     // output element offset of tile row `row` (< 128 of this group), channel `col` (M-range checked by the caller)
     // the store loops walk a lane's pixels m, m + RPI, m + 2 RPI, ... of the tile: (n, qh, qw) advanced by
     // additions instead of two integer divisions per 16-B store (~50 VALU each, 16 stores per lane and tile)
-    struct PixPos { int n, qh, qw; };
-    auto pix_of = [&](int m) -> PixPos {
-        PixPos q;
-        q.n = m / QQ;
-        const int rem = m - q.n * QQ;
-        q.qh = rem / ph.Qw;
-        q.qw = rem - q.qh * ph.Qw;
-        return q;
-    };
     auto pix_advance = [&](PixPos& q, int step) {
         q.qw += step;
         while (q.qw >= ph.Qw) {
@@ -1364,11 +1334,11 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_pp_kernel(GemmParams p) {
     // zeros), so the compiler's wait for the bias loads above them stays a counted one
     uint4 ypf[BNB ? NIT : 1];
     if constexpr (BNB) {
-        const __amdgpu_buffer_rsrc_t yrs = __builtin_amdgcn_make_buffer_rsrc((void*)p.bny, (short)0, p.ybytes, 0x00020000);
+        const __amdgpu_buffer_rsrc_t yrs = buf_rsrc(p.bny, p.ybytes);
         const int colb = nt * BN + wc * WCOLS + chx * EPC;
         const bool cok = rsub < RPI && colb < p.Co;
         const int cl = cok ? colb : 0;
-        PixPos pq = pix_of(mt * BM + 128 * grp + rsub);
+        PixPos pq = pix_of(mt * BM + 128 * grp + rsub, QQ, ph.Qw);
 #pragma unroll
         for (int it = 0; it < NIT; ++it) {
             const int row = it * RPI + rsub;
@@ -1384,12 +1354,12 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_pp_kernel(GemmParams p) {
     int rbase[RES ? 8 : 1];
     __amdgpu_buffer_rsrc_t rrs = xrs;
     if constexpr (RES) {
-        rrs = __builtin_amdgcn_make_buffer_rsrc((void*)p.res, (short)0, p.ybytes, 0x00020000);
+        rrs = buf_rsrc(p.res, p.ybytes);
 #pragma unroll
         for (int a = 0; a < 8; ++a) {
             const int m = mt * BM + 128 * grp + a * 16 + l16;
             const bool ok = m < M;
-            const PixPos q = pix_of(ok ? m : 0);
+            const PixPos q = pix_of(ok ? m : 0, QQ, ph.Qw);
             rbase[a] = ok ? (int)out_off(q, 0) * (int)sizeof(T) : -1;
         }
     }
@@ -1456,7 +1426,7 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_pp_kernel(GemmParams p) {
         // pass drain every outstanding access (the previous rows' stores included) at each row
         auto rows = [&](auto acc_c) {
             constexpr bool ACC = decltype(acc_c)::value;
-            PixPos pq = pix_of(mt * BM + 128 * grp + rsub);
+            PixPos pq = pix_of(mt * BM + 128 * grp + rsub, QQ, ph.Qw);
 #pragma unroll
             for (int it = 0; it < NIT; ++it) {
                 const int row = it * RPI + rsub;
@@ -1501,7 +1471,7 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_pp_kernel(GemmParams p) {
         const int col = nt * BN + wc * WCOLS + chx * EPC;
         auto rows = [&](auto acc_c) {
             constexpr bool ACC = decltype(acc_c)::value;
-            PixPos pq = pix_of(mt * BM + 128 * grp + rsub);
+            PixPos pq = pix_of(mt * BM + 128 * grp + rsub, QQ, ph.Qw);
 #pragma unroll 4
             for (int it = 0; it < NIT; ++it) {
                 const int row = it * RPI + rsub;
@@ -1564,7 +1534,7 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_pp_kernel(GemmParams p) {
             if (col < p.Co) {
                 const double s = (double)red[tid * 2] + (double)red[(BN + tid) * 2];
                 const double q = (double)red[tid * 2 + 1] + (double)red[(BN + tid) * 2 + 1];
-                const int rep = bid % SCD_STAT_REPLICAS;
+                const int rep = bid % SCD_STAT_REPLICAS;    // (mirrors stat_replica / stat_slot, gemm_common.h)
                 atomic_add_f64(p.stats + ((long)rep * 2 + 0) * p.Co + col, s);
                 atomic_add_f64(p.stats + ((long)rep * 2 + 1) * p.Co + col, q);
             }
@@ -1616,7 +1586,7 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_pp_kernel(GemmParams p) {
         if (half == 0 && m < M) {
 #pragma unroll
             for (int o = 0; o < 4; ++o) { a0[o] += xch[r * 8 + o]; a1[o] += xch[r * 8 + 4 + o]; }
-            const int n = m / QQ;
+            const int n = m / QQ;                              // (mirrors pix_of)
             const int rem = m - n * QQ;
             const int oh = rem / ph.Qw, ow = rem - (rem / ph.Qw) * ph.Qw;
             const long HWo = (long)p.Ho * p.Wo;
@@ -1667,35 +1637,26 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_heads384_kernel(GemmParams p
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int grp = wave >> 2, wc = wave & 3;
-    int bid;
-    {
-        const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = blockIdx.x & 7;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (blockIdx.x >> 3);
-    }
+    const int bid = xcd_tile_id();
     const scd_gemm_phase& ph = p.ph[0];
     const int QQ = ph.Qh * ph.Qw;
     const int M = p.N * QQ;
 
-    const int ntiles = (M + BM - 1) / BM;
     const int lrow = lane >> 3;
     const int cch = (lane & 7) ^ lrow;
     // A: this lane's DMA rows 96*grp + 32*j + 8*wc + lrow (j = third), byte offset at tap (0,0) + in-image tap mask
     int a_base[3];
     unsigned a_mask[3];
     auto tile_setup = [&](int mt) {
-    #pragma unroll
+#pragma unroll
         for (int j = 0; j < 3; ++j) {
             const int m = mt * BM + 96 * grp + 32 * j + 8 * wc + lrow;
             const bool ok = m < M;
-            const int mm = ok ? m : 0;
-            const int n = mm / QQ;
-            const int rem = mm - n * QQ;
-            const int qh = rem / ph.Qw;
-            const int qw = rem - qh * ph.Qw;
-            a_base[j] = ((n * p.Hi + qh) * p.Wi + qw) * p.Ci * 2 + cch * EPC * 2;
-            unsigned msk = 0;
+            const PixPos q = pix_of(ok ? m : 0, QQ, ph.Qw);
+            a_base[j] = ((q.n * p.Hi + q.qh) * p.Wi + q.qw) * p.Ci * 2 + cch * EPC * 2;
+            unsigned msk = 0;                              // (mirrors conv_gemm_pp_kernel's tap mask, stride 1)
             for (int t = 0; t < ph.ntaps; ++t) {
-                const int ih = qh + ph.dh[t], iw = qw + ph.dw[t];
+                const int ih = q.qh + ph.dh[t], iw = q.qw + ph.dw[t];
                 if (ok && (unsigned)ih < (unsigned)p.Hi && (unsigned)iw < (unsigned)p.Wi) msk |= 1u << t;
             }
             a_mask[j] = msk;
@@ -1703,12 +1664,12 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_heads384_kernel(GemmParams p
     };
     // B: rows 192*grp + 48*wc + 8*o + lrow, o = 0..5 (part 1: o < 3, part 2: o >= 3)
     int b_base[6];
-    #pragma unroll
+#pragma unroll
     for (int o = 0; o < 6; ++o) b_base[o] = ((192 * grp + 48 * wc + 8 * o + lrow) * p.wrow + cch * EPC) * 2;
     const int cpt = p.Ci / BK;
     const int KT = ph.ntaps * cpt;
-    const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, (short)0, p.xbytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, (short)0, p.wbytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t xrs = buf_rsrc(p.x, p.xbytes);
+    const __amdgpu_buffer_rsrc_t wrs = buf_rsrc(p.w, p.wbytes);
 
     // Serpentine K order: every workgroup reads the whole 1.77-MB weight operand in K order, and by the time an XCD's
     // next round of tiles starts, its 4-MB L2 has streamed that round's input rows too, so the first K-stages'
@@ -1716,6 +1677,7 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_heads384_kernel(GemmParams p
     // round, 32 per XCD) walk K backwards, starting on the stages the previous round used last.  The fp32 summation
     // order of those tiles changes; it is fixed per tile index, so every run gives the same bits.
     const bool krev = p.kserp && ((blockIdx.x >> 8) & 1);
+    // (mirrors conv_gemm_pp_kernel's stage_args, plus krev)
     struct StageArgs { int live, tap, adelta, bdelta; };
     auto stage_args = [&](int kt_req) {
         StageArgs a;
@@ -1735,7 +1697,7 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_heads384_kernel(GemmParams p
     };
     auto issue_b = [&](const StageArgs& g, char* buf, int part) {
         char* Bs = buf + BM * 128;
-    #pragma unroll
+#pragma unroll
         for (int o = 3 * part; o < 3 * part + 3; ++o)
             dma16(wrs, Bs + (192 * grp + 48 * wc + 8 * o) * 128, sel_off(g.live, b_base[o] + g.bdelta));
     };
@@ -1748,214 +1710,206 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_heads384_kernel(GemmParams p
         issue_a(g0, smem, 1);
         issue_a(g0, smem, 2);
     };
-    {
-        const int mt = bid;
-        (void)ntiles;
-        tile_setup(mt);
-        if (KT > 0) issue_stage0();
-        const int l16 = lane & 15, lg = lane >> 4;
-        const int l7 = l16 & 7;
-        const int co0 = ((0 * 4 + lg) ^ l7) << 4, co1 = ((1 * 4 + lg) ^ l7) << 4;
-        f32x4 acc[NA][NB];
-    #pragma unroll
-        for (int a = 0; a < NA; ++a)
-    #pragma unroll
-            for (int b = 0; b < NB; ++b) acc[a][b] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        h16x8 bfr[NB][2], af[2][2];
+    const int mt = bid;
+    tile_setup(mt);
+    if (KT > 0) issue_stage0();
+    const int l16 = lane & 15, lg = lane >> 4;
+    const int l7 = l16 & 7;
+    const int co0 = ((0 * 4 + lg) ^ l7) << 4, co1 = ((1 * 4 + lg) ^ l7) << 4;
+    f32x4 acc[NA][NB];
+#pragma unroll
+    for (int a = 0; a < NA; ++a)
+#pragma unroll
+        for (int b = 0; b < NB; ++b) acc[a][b] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    h16x8 bfr[NB][2], af[2][2];
 
-        auto read_b = [&](const char* buf) {
-            const char* Bs = buf + BM * 128;
-    #pragma unroll
-            for (int b = 0; b < NB; ++b) {
-                const char* row = Bs + (96 * wc + 16 * b + l16) * 128;
-                bfr[b][0] = *(const h16x8*)(row + co0);
-                bfr[b][1] = *(const h16x8*)(row + co1);
-            }
-        };
-        auto read_a = [&](const char* buf, int q) {
-    #pragma unroll
-            for (int a = 0; a < 2; ++a) {
-                const char* row = buf + (96 * grp + 32 * q + 16 * a + l16) * 128;
-                af[a][0] = *(const h16x8*)(row + co0);
-                af[a][1] = *(const h16x8*)(row + co1);
-            }
-        };
-        auto mfma_q = [&](int q) {
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_setprio(1);
-    #pragma unroll
-            for (int s = 0; s < 2; ++s)
-    #pragma unroll
-                for (int a = 0; a < 2; ++a)
-    #pragma unroll
-                    for (int b = 0; b < NB; ++b)
-                        acc[2 * q + a][b] = mfma_16x16x32_h16(bfr[b][s], af[a][s], acc[2 * q + a][b]);
-            __builtin_amdgcn_s_setprio(0);
-            __builtin_amdgcn_sched_barrier(0);
-        };
-        auto bar = [&]() {
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_barrier();
-            __builtin_amdgcn_sched_barrier(0);
-        };
-
-        SCD_STAMP_BEGIN();
-        if (KT > 0) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            bar();
-            if (grp == 1) bar();                 // stagger: group 1 runs one barrier behind
-            for (int t = 0; t < KT; ++t) {
-                char* cur = smem + (t & 1) * STAGE;
-                char* nxt = smem + ((t & 1) ^ 1) * STAGE;
-                const StageArgs g = stage_args(t + 1);
-                // P1
-                read_b(cur);
-                read_a(cur, 0);
-                issue_a(g, nxt, 0);
-                issue_b(g, nxt, 0);
-                bar();
-                mfma_q(0);
-                asm volatile("s_waitcnt vmcnt(5)" ::: "memory");     // A third 1 (P3 of t-1)
-                bar();
-                // P2
-                read_a(cur, 1);
-                issue_b(g, nxt, 1);
-                bar();
-                mfma_q(1);
-                asm volatile("s_waitcnt vmcnt(7)" ::: "memory");     // A third 2 of this stage
-                bar();
-                // P3
-                read_a(cur, 2);
-                issue_a(g, nxt, 1);
-                issue_a(g, nxt, 2);
-                asm volatile("s_waitcnt vmcnt(2)" ::: "memory");     // next stage: A third 0 and every B row
-                bar();
-                mfma_q(2);
-                bar();
-            }
-            if (grp == 0) bar();
+    auto read_b = [&](const char* buf) {
+        const char* Bs = buf + BM * 128;
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+            const char* row = Bs + (96 * wc + 16 * b + l16) * 128;
+            bfr[b][0] = *(const h16x8*)(row + co0);
+            bfr[b][1] = *(const h16x8*)(row + co1);
         }
+    };
+    auto read_a = [&](const char* buf, int q) {
+#pragma unroll
+        for (int a = 0; a < 2; ++a) {
+            const char* row = buf + (96 * grp + 32 * q + 16 * a + l16) * 128;
+            af[a][0] = *(const h16x8*)(row + co0);
+            af[a][1] = *(const h16x8*)(row + co1);
+        }
+    };
+    auto mfma_q = [&](int q) {
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+#pragma unroll
+            for (int a = 0; a < 2; ++a)
+#pragma unroll
+                for (int b = 0; b < NB; ++b)
+                    acc[2 * q + a][b] = mfma_16x16x32_h16(bfr[b][s], af[a][s], acc[2 * q + a][b]);
+        __builtin_amdgcn_s_setprio(0);
+        __builtin_amdgcn_sched_barrier(0);
+    };
+
+    SCD_STAMP_BEGIN();
+    if (KT > 0) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        SCD_STAMP_END();
-        // ---- epilogue from the accumulators.  Lane (l16, lg) of block (a, b) holds hidden channels
-        // 96wc + 16b + 4lg .. +3 of pixel 96grp + 16a + l16: after bias + ReLU those 4 bf16 are (1) an 8-B piece of
-        // the pixel's NHWC row, stored at once, and (2) exactly the B operand of a 16x16x16 MFMA (B[k = 4lg + j][n =
-        // l16]), so the 1x1 tails out[o][px] = sum_c W1[o][c] hid[c][px] run on the same registers: A = the
-        // block-diagonal W1 slice of the wave's 16 channels (A[m = l16][k = 4lg + j], fp32 weights as bf16 hi + lo,
-        // ~2^-17), 12 MFMAs per 16-pixel block.  The four channel waves of a group meet in LDS (48 KiB of fp32
-        // partials), then one pass adds them, the bias, and writes the NCHW fp32 outputs.
-        {
-            typedef __attribute__((ext_vector_type(4))) h16 bf16x4;
-            const int od0 = p.head_od[0], od1 = p.head_od[1], od2 = p.head_od[2];
-            const int odsum = od0 + od1 + od2;
-            const int o = l16;                                       // tail output row of this lane's W1 fragment
-            const int hh = o < od0 ? 0 : o < od0 + od1 ? 1 : o < odsum ? 2 : -1;
-            const int oo = hh == 0 ? o : hh == 1 ? o - od0 : o - od0 - od1;
-            const float* wsel = hh == 0 ? p.head_w[0] : hh == 1 ? p.head_w[1] : p.head_w[2];
-            f32x4 tl[NA];
-    #pragma unroll
-            for (int a = 0; a < NA; ++a) tl[a] = (f32x4){0.f, 0.f, 0.f, 0.f};
-            // blocks in pairs (b, b+1): after the tails, v_permlane16_swap trades the odd rows' block-b halves for
-            // the even rows' block-(b+1) halves, so every lane holds 8 consecutive channels (16-B stores: even rows
-            // channels 16b + 4lg .., odd rows 16(b+1) + 4(lg-1) ..; 64 contiguous bytes per pixel and instruction)
-            // hidden channels >= hid_cols are stored only at the pixels the keep map names (the size / offset heads'
-            // sparse backward reads them there only; HeadsFn recomputes the whole tensor for any other backward)
-            unsigned keep = (1u << NA) - 1;
-            if (p.hid_keep) {                                        // the NA loads together, one wait
-                unsigned char kv[NA];
-    #pragma unroll
-                for (int a = 0; a < NA; ++a) {
-                    const int m = mt * BM + 96 * grp + 16 * a + l16;
-                    kv[a] = p.hid_keep[m < M ? m : 0];
-                }
-                keep = 0;
-    #pragma unroll
-                for (int a = 0; a < NA; ++a)
-                    if (mt * BM + 96 * grp + 16 * a + l16 < M && kv[a]) keep |= 1u << a;
+        pp_barrier();
+        if (grp == 1) pp_barrier();                 // stagger: group 1 runs one barrier behind
+        for (int t = 0; t < KT; ++t) {
+            char* cur = smem + (t & 1) * STAGE;
+            char* nxt = smem + ((t & 1) ^ 1) * STAGE;
+            const StageArgs g = stage_args(t + 1);
+            // P1
+            read_b(cur);
+            read_a(cur, 0);
+            issue_a(g, nxt, 0);
+            issue_b(g, nxt, 0);
+            pp_barrier();
+            mfma_q(0);
+            asm volatile("s_waitcnt vmcnt(5)" ::: "memory");     // A third 1 (P3 of t-1)
+            pp_barrier();
+            // P2
+            read_a(cur, 1);
+            issue_b(g, nxt, 1);
+            pp_barrier();
+            mfma_q(1);
+            asm volatile("s_waitcnt vmcnt(7)" ::: "memory");     // A third 2 of this stage
+            pp_barrier();
+            // P3
+            read_a(cur, 2);
+            issue_a(g, nxt, 1);
+            issue_a(g, nxt, 2);
+            asm volatile("s_waitcnt vmcnt(2)" ::: "memory");     // next stage: A third 0 and every B row
+            pp_barrier();
+            mfma_q(2);
+            pp_barrier();
+        }
+        if (grp == 0) pp_barrier();
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    SCD_STAMP_END();
+    // ---- epilogue from the accumulators.  Lane (l16, lg) of block (a, b) holds hidden channels
+    // 96wc + 16b + 4lg .. +3 of pixel 96grp + 16a + l16: after bias + ReLU those 4 bf16 are (1) an 8-B piece of
+    // the pixel's NHWC row, stored at once, and (2) exactly the B operand of a 16x16x16 MFMA (B[k = 4lg + j][n =
+    // l16]), so the 1x1 tails out[o][px] = sum_c W1[o][c] hid[c][px] run on the same registers: A = the
+    // block-diagonal W1 slice of the wave's 16 channels (A[m = l16][k = 4lg + j], fp32 weights as bf16 hi + lo,
+    // ~2^-17), 12 MFMAs per 16-pixel block.  The four channel waves of a group meet in LDS (48 KiB of fp32
+    // partials), then one pass adds them, the bias, and writes the NCHW fp32 outputs.
+    {
+        typedef __attribute__((ext_vector_type(4))) h16 bf16x4;
+        const int od0 = p.head_od[0], od1 = p.head_od[1], od2 = p.head_od[2];
+        const int odsum = od0 + od1 + od2;
+        const int o = l16;                                       // tail output row of this lane's W1 fragment
+        const int hh = o < od0 ? 0 : o < od0 + od1 ? 1 : o < odsum ? 2 : -1;
+        const int oo = hh == 0 ? o : hh == 1 ? o - od0 : o - od0 - od1;
+        const float* wsel = hh == 0 ? p.head_w[0] : hh == 1 ? p.head_w[1] : p.head_w[2];
+        f32x4 tl[NA];
+#pragma unroll
+        for (int a = 0; a < NA; ++a) tl[a] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        // blocks in pairs (b, b+1): after the tails, v_permlane16_swap trades the odd rows' block-b halves for
+        // the even rows' block-(b+1) halves, so every lane holds 8 consecutive channels (16-B stores: even rows
+        // channels 16b + 4lg .., odd rows 16(b+1) + 4(lg-1) ..; 64 contiguous bytes per pixel and instruction)
+        // hidden channels >= hid_cols are stored only at the pixels the keep map names (the size / offset heads'
+        // sparse backward reads them there only; HeadsFn recomputes the whole tensor for any other backward)
+        unsigned keep = (1u << NA) - 1;
+        if (p.hid_keep) {                                        // the NA loads together, one wait
+            unsigned char kv[NA];
+#pragma unroll
+            for (int a = 0; a < NA; ++a) {
+                const int m = mt * BM + 96 * grp + 16 * a + l16;
+                kv[a] = p.hid_keep[m < M ? m : 0];
             }
-            // the bias and W1 slices of all NB blocks loaded up front, unconditionally (from a valid address, the
-            // value selected after): a load inside the block loop, or under a branch, makes the compiler wait for
-            // every access before it -- the previous blocks' hidden-row stores included
-            hx4 whi[NB], wlo[NB];
-            float bias[NB][4];
-    #pragma unroll
-            for (int b = 0; b < NB; ++b) {
-                const int col0 = 96 * wc + 16 * b + 4 * lg;
-                const float4 bb = *(const float4*)(p.bias + col0);
-                bias[b][0] = bb.x; bias[b][1] = bb.y; bias[b][2] = bb.z; bias[b][3] = bb.w;
-                // W1[o][col0 .. col0 + 3] when those channels belong to output o's head, else 0
-                const bool wok = hh >= 0 && (col0 >> 7) == hh;
-                const float4 wl = *(const float4*)((hh >= 0 ? wsel : p.head_w[0]) + (wok ? oo * 128 + (col0 & 127) : 0));
-                const float4 wv = wok ? wl : make_float4(0.f, 0.f, 0.f, 0.f);
-                const float w4[4] = {wv.x, wv.y, wv.z, wv.w};
-    #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    whi[b][j] = (h16)w4[j];
-                    wlo[b][j] = (h16)(w4[j] - (float)whi[b][j]);
-                }
-            }
-            // consumed here, before the first store (else the compiler's wait for the last ones lands after stores)
-    #pragma unroll
-            for (int b = 0; b < NB; ++b)
-                asm volatile("" : "+v"(whi[b]), "+v"(wlo[b]), "+v"(bias[b][0]), "+v"(bias[b][1]), "+v"(bias[b][2]),
-                             "+v"(bias[b][3]));
-    #pragma unroll
-            for (int b = 0; b < NB; b += 2) {
-                const int colst = 96 * wc + 16 * b + ((lg & 1) ? 16 + 4 * (lg - 1) : 4 * lg);
-    #pragma unroll
-                for (int a = 0; a < NA; ++a) {
-                    hx4 hv[2];
-    #pragma unroll
-                    for (int e = 0; e < 2; ++e)
-    #pragma unroll
-                        for (int r = 0; r < 4; ++r) hv[e][r] = (h16)fmaxf(acc[a][b + e][r] + bias[b + e][r], 0.f);
-    #pragma unroll
-                    for (int e = 0; e < 2; ++e) {
-                        tl[a] = mfma_16x16x16(whi[b + e], hv[e], tl[a]);
-                        tl[a] = mfma_16x16x16(wlo[b + e], hv[e], tl[a]);
-                    }
-                    typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
-                    const u32x2 x = __builtin_bit_cast(u32x2, hv[0]), y = __builtin_bit_cast(u32x2, hv[1]);
-                    uint4 st;
-                    {
-                        const auto s0 = __builtin_amdgcn_permlane16_swap(x[0], y[0], false, false);
-                        const auto s1 = __builtin_amdgcn_permlane16_swap(x[1], y[1], false, false);
-                        st.x = s0[0]; st.y = s1[0]; st.z = s0[1]; st.w = s1[1];
-                    }
-                    const int m = mt * BM + 96 * grp + 16 * a + l16;
-                    if (m < M && (colst < p.hid_cols || ((keep >> a) & 1u)))
-                        *(uint4*)(p.y + ((long)m * BN + colst) * 2) = st;
-                }
-            }
-            {
-                // partials [wc][o][pixel of tile]: D[o = 4lg + r][px = l16] of block a
-                float* part = (float*)smem;
-    #pragma unroll
-                for (int a = 0; a < NA; ++a)
-    #pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        part[(wc * 16 + 4 * lg + r) * BM + 96 * grp + 16 * a + l16] = tl[a][r];
-                __syncthreads();
-                for (int idx = tid; idx < odsum * BM; idx += 512) {
-                    const int oi = idx / BM, r = idx - oi * BM;
-                    const int m = mt * BM + r;
-                    if (m >= M) continue;
-                    const float v = (part[(0 * 16 + oi) * BM + r] + part[(1 * 16 + oi) * BM + r]) +
-                                    (part[(2 * 16 + oi) * BM + r] + part[(3 * 16 + oi) * BM + r]);
-                    const int h = oi < od0 ? 0 : oi < od0 + od1 ? 1 : 2;
-                    const int ob = oi - (h == 0 ? 0 : h == 1 ? od0 : od0 + od1);
-                    const int odh = h == 0 ? od0 : h == 1 ? od1 : od2;
-                    float* out = h == 0 ? p.head_out[0] : h == 1 ? p.head_out[1] : p.head_out[2];
-                    const float bo = (h == 0 ? p.head_b[0] : h == 1 ? p.head_b[1] : p.head_b[2])[ob];
-                    const int n = m / QQ, pix = m - (m / QQ) * QQ;
-                    out[((long)n * odh + ob) * QQ + pix] = v + bo;
-                }
+            keep = 0;
+#pragma unroll
+            for (int a = 0; a < NA; ++a)
+                if (mt * BM + 96 * grp + 16 * a + l16 < M && kv[a]) keep |= 1u << a;
+        }
+        // the bias and W1 slices of all NB blocks loaded up front, unconditionally (from a valid address, the
+        // value selected after): a load inside the block loop, or under a branch, makes the compiler wait for
+        // every access before it -- the previous blocks' hidden-row stores included
+        hx4 whi[NB], wlo[NB];
+        float bias[NB][4];
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+            const int col0 = 96 * wc + 16 * b + 4 * lg;
+            const float4 bb = *(const float4*)(p.bias + col0);
+            bias[b][0] = bb.x; bias[b][1] = bb.y; bias[b][2] = bb.z; bias[b][3] = bb.w;
+            // W1[o][col0 .. col0 + 3] when those channels belong to output o's head, else 0
+            const bool wok = hh >= 0 && (col0 >> 7) == hh;
+            const float4 wl = *(const float4*)((hh >= 0 ? wsel : p.head_w[0]) + (wok ? oo * 128 + (col0 & 127) : 0));
+            const float4 wv = wok ? wl : make_float4(0.f, 0.f, 0.f, 0.f);
+            const float w4[4] = {wv.x, wv.y, wv.z, wv.w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                whi[b][j] = (h16)w4[j];
+                wlo[b][j] = (h16)(w4[j] - (float)whi[b][j]);
             }
         }
-        __syncthreads();                 // staging consumed before the next tile's prologue DMA
+        // consumed here, before the first store (else the compiler's wait for the last ones lands after stores)
+#pragma unroll
+        for (int b = 0; b < NB; ++b)
+            asm volatile("" : "+v"(whi[b]), "+v"(wlo[b]), "+v"(bias[b][0]), "+v"(bias[b][1]), "+v"(bias[b][2]),
+                         "+v"(bias[b][3]));
+#pragma unroll
+        for (int b = 0; b < NB; b += 2) {
+            const int colst = 96 * wc + 16 * b + ((lg & 1) ? 16 + 4 * (lg - 1) : 4 * lg);
+#pragma unroll
+            for (int a = 0; a < NA; ++a) {
+                hx4 hv[2];
+#pragma unroll
+                for (int e = 0; e < 2; ++e)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) hv[e][r] = (h16)fmaxf(acc[a][b + e][r] + bias[b + e][r], 0.f);
+#pragma unroll
+                for (int e = 0; e < 2; ++e) {
+                    tl[a] = mfma_16x16x16(whi[b + e], hv[e], tl[a]);
+                    tl[a] = mfma_16x16x16(wlo[b + e], hv[e], tl[a]);
+                }
+                typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
+                const u32x2 x = __builtin_bit_cast(u32x2, hv[0]), y = __builtin_bit_cast(u32x2, hv[1]);
+                uint4 st;
+                {
+                    const auto s0 = __builtin_amdgcn_permlane16_swap(x[0], y[0], false, false);
+                    const auto s1 = __builtin_amdgcn_permlane16_swap(x[1], y[1], false, false);
+                    st.x = s0[0]; st.y = s1[0]; st.z = s0[1]; st.w = s1[1];
+                }
+                const int m = mt * BM + 96 * grp + 16 * a + l16;
+                if (m < M && (colst < p.hid_cols || ((keep >> a) & 1u)))
+                    *(uint4*)(p.y + ((long)m * BN + colst) * 2) = st;
+            }
+        }
+        {
+            // partials [wc][o][pixel of tile]: D[o = 4lg + r][px = l16] of block a
+            float* part = (float*)smem;
+#pragma unroll
+            for (int a = 0; a < NA; ++a)
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    part[(wc * 16 + 4 * lg + r) * BM + 96 * grp + 16 * a + l16] = tl[a][r];
+            __syncthreads();
+            for (int idx = tid; idx < odsum * BM; idx += 512) {
+                const int oi = idx / BM, r = idx - oi * BM;
+                const int m = mt * BM + r;
+                if (m >= M) continue;
+                const float v = (part[(0 * 16 + oi) * BM + r] + part[(1 * 16 + oi) * BM + r]) +
+                                (part[(2 * 16 + oi) * BM + r] + part[(3 * 16 + oi) * BM + r]);
+                const int h = oi < od0 ? 0 : oi < od0 + od1 ? 1 : 2;
+                const int ob = oi - (h == 0 ? 0 : h == 1 ? od0 : od0 + od1);
+                const int odh = h == 0 ? od0 : h == 1 ? od1 : od2;
+                float* out = h == 0 ? p.head_out[0] : h == 1 ? p.head_out[1] : p.head_out[2];
+                const float bo = (h == 0 ? p.head_b[0] : h == 1 ? p.head_b[1] : p.head_b[2])[ob];
+                const int n = m / QQ, pix = m - (m / QQ) * QQ;
+                out[((long)n * odh + ob) * QQ + pix] = v + bo;
+            }
+        }
     }
+    __syncthreads();                 // staging consumed before the next tile's prologue DMA
 }
 
 constexpr int WGRAD_OCC = 2;  // register-staged weight-gradient kernel: workgroups per CU the registers are budgeted for
@@ -1994,13 +1948,26 @@ __device__ __forceinline__ bool wgrad_block(const WgradParams& p, int& z, int& m
     return z < p.nsplit;
 }
 
-// LDS image of a [pixel][channel] stage for transposed (ds_read_b64_tr_b16) fragment reads: a row
-// stride of 8 dwords mod 64 banks (288 B for <= 256-B rows, 544 B for 512-B rows) puts rows r..r+3 on
-// disjoint 8-bank slots, and the column offset of rows with bit 3 set is XORed with 128 B, so rows
-// {0-3, 8-11} read by one 32-lane half cover all 64 banks: the transposed reads are conflict free.
-__host__ __device__ constexpr int wrow_stride(int rowbytes) { return rowbytes <= 256 ? 288 : rowbytes + 32; }
-__device__ __forceinline__ int wswz(int row, int byte, int stride) {
-    return row * stride + (byte ^ (((row >> 3) & 1) << 7));
+// Weight-gradient stage cursor: output position (n, oh, ow) of a stage's first pixel, workgroup-uniform (kept in scalar
+// registers).  A stage of kp pixels is part of one output row or `rows` whole rows
+__device__ __forceinline__ void stage_cursor_init(int pix0, int Ho, int Wo, int& sn, int& soh, int& sow) {
+    const int HoWo = Ho * Wo;
+    sn = __builtin_amdgcn_readfirstlane(pix0 / HoWo);
+    const int rem = pix0 - sn * HoWo;
+    soh = __builtin_amdgcn_readfirstlane(rem / Wo);
+    sow = __builtin_amdgcn_readfirstlane(rem - soh * Wo);
+}
+__device__ __forceinline__ void stage_cursor_step(int kp, int rows, int Ho, int Wo, int& sn, int& soh, int& sow) {
+    sow += kp;
+    const bool wrap = sow >= Wo;
+    sow = wrap ? 0 : sow;
+    soh += wrap ? rows : 0;
+    const bool wrap2 = soh >= Ho;
+    soh = wrap2 ? 0 : soh;
+    sn += wrap2 ? 1 : 0;
+    sn = __builtin_amdgcn_readfirstlane(sn);
+    soh = __builtin_amdgcn_readfirstlane(soh);
+    sow = __builtin_amdgcn_readfirstlane(sow);
 }
 
 // FASTX: a KP-pixel stage never straddles an image and covers either part of one output row (Wo % KP == 0)
@@ -2068,11 +2035,7 @@ __global__ __launch_bounds__(256, WGRAD_OCC) void conv_wgrad_kernel(WgradParams 
     constexpr int NXS = FASTX == 2 ? XCH : 1;
     int xA[NXS], xB[NXS], xL[NXS];
     if constexpr (FASTX != 0) {
-        const int HoWo = p.Ho * p.Wo;
-        sn = __builtin_amdgcn_readfirstlane(pix0 / HoWo);
-        const int rem = pix0 - sn * HoWo;
-        soh = __builtin_amdgcn_readfirstlane(rem / p.Wo);
-        sow = __builtin_amdgcn_readfirstlane(rem - soh * p.Wo);
+        stage_cursor_init(pix0, p.Ho, p.Wo, sn, soh, sow);
 #pragma unroll
         for (int i = 0; i < NXS; ++i) {
             const int rr = xr0 + i * XRS;
@@ -2083,19 +2046,14 @@ __global__ __launch_bounds__(256, WGRAD_OCC) void conv_wgrad_kernel(WgradParams 
         }
     }
     auto advance = [&]() {     // every row advances by KP pixels
-        if constexpr (FASTX != 0) {
-            if (FASTX == 1) {
-                sow += KP;
-                const bool wrap = sow >= p.Wo;
-                sow = wrap ? 0 : sow;
-                soh += wrap ? 1 : 0;
-            } else {
-                soh += KP / p.Wo;
-            }
+        if constexpr (FASTX == 1) {
+            stage_cursor_step(KP, 1, p.Ho, p.Wo, sn, soh, sow);
+        } else if constexpr (FASTX == 2) {
+            // whole rows, sow stays 0 (mirrors stage_cursor_step without its column wrap)
+            soh += KP / p.Wo;
             const bool wrap2 = soh >= p.Ho;
             soh = wrap2 ? 0 : soh;
             sn += wrap2 ? 1 : 0;
-            // workgroup-uniform: keep the cursor in scalar registers
             sn = __builtin_amdgcn_readfirstlane(sn);
             soh = __builtin_amdgcn_readfirstlane(soh);
             sow = __builtin_amdgcn_readfirstlane(sow);
@@ -2111,8 +2069,8 @@ __global__ __launch_bounds__(256, WGRAD_OCC) void conv_wgrad_kernel(WgradParams 
         }
     };
 
-    const __amdgpu_buffer_rsrc_t grs = __builtin_amdgcn_make_buffer_rsrc((void*)p.g, (short)0, p.gbytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, (short)0, p.xbytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t grs = buf_rsrc(p.g, p.gbytes);
+    const __amdgpu_buffer_rsrc_t xrs = buf_rsrc(p.x, p.xbytes);
     auto gload = [&](int k0, uint4 (&rg)[GCH], uint4 (&rx)[XCH]) {
         if constexpr (FASTX != 0) {
             const int S = __builtin_amdgcn_readfirstlane(((sn * p.Hi + p.is * soh) * p.Wi + p.is * sow) * p.Ci);
@@ -2193,6 +2151,7 @@ __global__ __launch_bounds__(256, WGRAD_OCC) void conv_wgrad_kernel(WgradParams 
 #pragma unroll
                 for (int a = 0; a < 4; ++a) {
                     const int cb = (wm * 64 + a * 16 + 4 * pp) * 2;
+                    // (mirrors tr16_frag, gemm_common.h)
                     s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(Gs + wswz(r0, cb, GROW)));
                     s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(Gs + wswz(r0 + 4, cb, GROW)));
                     s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
@@ -2347,14 +2306,8 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_pp2_kernel(WgradParams p) {
     }
     const int rows_per_wrap = p.Wo >= KP ? 1 : KP / p.Wo;    // output rows a stage advances when it wraps
     int sn, soh, sow;
-    {
-        const int HoWo = p.Ho * p.Wo;
-        sn = __builtin_amdgcn_readfirstlane(pix0 / HoWo);
-        const int rem = pix0 - sn * HoWo;
-        soh = __builtin_amdgcn_readfirstlane(rem / p.Wo);
-        sow = __builtin_amdgcn_readfirstlane(rem - soh * p.Wo);
-    }
-    auto advance = [&]() {
+    stage_cursor_init(pix0, p.Ho, p.Wo, sn, soh, sow);
+    auto advance = [&]() {     // (mirrors stage_cursor_step)
         sow += KP;
         const bool wrap = sow >= p.Wo;
         sow = wrap ? 0 : sow;
@@ -2366,8 +2319,8 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_pp2_kernel(WgradParams p) {
         soh = __builtin_amdgcn_readfirstlane(soh);
         sow = __builtin_amdgcn_readfirstlane(sow);
     };
-    const __amdgpu_buffer_rsrc_t grs = __builtin_amdgcn_make_buffer_rsrc((void*)p.g, (short)0, p.gbytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, (short)0, p.xbytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t grs = buf_rsrc(p.g, p.gbytes);
+    const __amdgpu_buffer_rsrc_t xrs = buf_rsrc(p.x, p.xbytes);
     // stage whose first pixel is k0 (cursor = its position)
     auto issue_x = [&](int k0, char* stg, int half) {
         const int S = __builtin_amdgcn_readfirstlane(((sn * p.Hi + p.is * soh) * p.Wi + p.is * sow) * p.Ci);
@@ -2389,13 +2342,6 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_pp2_kernel(WgradParams p) {
 
     const int l16 = lane & 15, lg = lane >> 4;
     const int q4 = l16 >> 2, pp = l16 & 3;
-    typedef __attribute__((ext_vector_type(8))) short s16x8;
-    auto trf = [&](const char* lo_addr, const char* hi_addr) {
-        s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)lo_addr);
-        s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)hi_addr);
-        s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        return __builtin_bit_cast(h16x8, v);
-    };
     f32x4 acc[2 * NQ][4];
 #pragma unroll
     for (int a = 0; a < 2 * NQ; ++a)
@@ -2412,7 +2358,7 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_pp2_kernel(WgradParams p) {
             for (int b = 0; b < 4; ++b) {
                 const int cb = (wc * 64 + b * 16 + 4 * pp) * 2;
                 const int pr = cb >> 5, lo8 = cb & 31;
-                xf[b][s] = trf(X + r0 * 512 + ((pr ^ f0) << 5) + lo8, X + (r0 + 4) * 512 + ((pr ^ f1) << 5) + lo8);
+                xf[b][s] = tr16_frag(X + r0 * 512 + ((pr ^ f0) << 5) + lo8, X + (r0 + 4) * 512 + ((pr ^ f1) << 5) + lo8);
             }
         }
     };
@@ -2424,7 +2370,7 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_pp2_kernel(WgradParams p) {
 #pragma unroll
             for (int a = 0; a < 2; ++a) {
                 const int plo = a ^ ((r0 >> 3) & 1), phi = a ^ (((r0 + 4) >> 3) & 1);
-                gf[a][s] = trf(G + r0 * 64 + plo * 32 + 8 * pp, G + (r0 + 4) * 64 + phi * 32 + 8 * pp);
+                gf[a][s] = tr16_frag(G + r0 * 64 + plo * 32 + 8 * pp, G + (r0 + 4) * 64 + phi * 32 + 8 * pp);
             }
         }
     };
@@ -2440,11 +2386,6 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_pp2_kernel(WgradParams p) {
                 for (int b = 0; b < 4; ++b)
                     acc[2 * q + a][b] = mfma_16x16x32_h16(xf[b][s], gf[a][s], acc[2 * q + a][b]);
         __builtin_amdgcn_s_setprio(0);
-        __builtin_amdgcn_sched_barrier(0);
-    };
-    auto bar = [&]() {
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
     };
 
@@ -2466,8 +2407,8 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_pp2_kernel(WgradParams p) {
         } else {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
-        bar();
-        if (grp == 1) bar();
+        pp_barrier();
+        if (grp == 1) pp_barrier();
         // schedule (stage t fetches stage t+1 into the other buffer): phase 1: X half 0, phase 2: X half 1,
         // phases 3(-4): the G quarters.  NQ 4: C2 vmcnt(4), L4 vmcnt(4), C4 vmcnt(2);
         // NQ 3: C1 vmcnt(3), C2 vmcnt(4), L3 vmcnt(3), C3 vmcnt(2);
@@ -2502,13 +2443,13 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_pp2_kernel(WgradParams p) {
                             else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                         }
                     }
-                    bar();
+                    pp_barrier();
                     mfma_q(q, gf);
                     if (q == 1 && grp == 0) {
                         if constexpr (NBUF == 3) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
                         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                     }
-                    bar();
+                    pp_barrier();
                     continue;
                 }
                 if (q < 2) issue_x(k1, nxt, q);
@@ -2518,7 +2459,7 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_pp2_kernel(WgradParams p) {
                 } else {
                     if (q == 2) { issue_g(k1, nxt, 0); issue_g(k1, nxt, 1); issue_g(k1, nxt, 2); advance(); asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); }
                 }
-                bar();
+                pp_barrier();
                 mfma_q(q, gf);
                 if constexpr (NQ == 4) {
                     if (q == 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
@@ -2528,10 +2469,10 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_pp2_kernel(WgradParams p) {
                     if (q == 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
                     if (q == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
                 }
-                bar();
+                pp_barrier();
             }
         }
-        if (grp == 0) bar();
+        if (grp == 0) pp_barrier();
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     // fp32 slab: lane holds columns kk..kk+3 of channel row cg for every (m, b) block
@@ -2607,27 +2548,10 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_l1_kernel(WgradParams p) {
     const int g_c8 = ((lane & 7) ^ (l1w_f(g_R) << 1)) * 8;
 
     int sn, soh, sow;
-    {
-        const int HW = H * W;
-        sn = __builtin_amdgcn_readfirstlane(pix0 / HW);
-        const int rem = pix0 - sn * HW;
-        soh = __builtin_amdgcn_readfirstlane(rem / W);
-        sow = __builtin_amdgcn_readfirstlane(rem - soh * W);
-    }
-    auto advance = [&]() {
-        sow += L1W_KP;
-        const bool wrap = sow >= W;
-        sow = wrap ? 0 : sow;
-        soh += wrap ? 1 : 0;
-        const bool wrap2 = soh >= H;
-        soh = wrap2 ? 0 : soh;
-        sn += wrap2 ? 1 : 0;
-        sn = __builtin_amdgcn_readfirstlane(sn);
-        soh = __builtin_amdgcn_readfirstlane(soh);
-        sow = __builtin_amdgcn_readfirstlane(sow);
-    };
-    const __amdgpu_buffer_rsrc_t grs = __builtin_amdgcn_make_buffer_rsrc((void*)p.g, (short)0, p.gbytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, (short)0, p.xbytes, 0x00020000);
+    stage_cursor_init(pix0, H, W, sn, soh, sow);
+    auto advance = [&]() { stage_cursor_step(L1W_KP, 1, H, W, sn, soh, sow); };
+    const __amdgpu_buffer_rsrc_t grs = buf_rsrc(p.g, p.gbytes);
+    const __amdgpu_buffer_rsrc_t xrs = buf_rsrc(p.x, p.xbytes);
     auto issue = [&](int k0, char* buf) {
         const int S = __builtin_amdgcn_readfirstlane(((sn * H + soh) * W + sow) * 64);
 #pragma unroll
@@ -2647,13 +2571,6 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_l1_kernel(WgradParams p) {
     const int l16 = lane & 15, lg = lane >> 4;
     const int q4 = l16 >> 2, pp = l16 & 3;
     const int r0 = 8 * lg + q4;                      // fragment row of k-step 0 (k-step 1: + 32 rows = + 4096 B)
-    typedef __attribute__((ext_vector_type(8))) short s16x8;
-    auto trf = [&](const char* lo_addr, const char* hi_addr) {
-        s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)lo_addr);
-        s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)hi_addr);
-        s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        return __builtin_bit_cast(h16x8, v);
-    };
     // per-lane byte offsets: halo (tap column dw, lo/hi rows) and output gradient (block a; hi = lo + 4 rows)
     int xo[3][2], go[4];
 #pragma unroll
@@ -2671,11 +2588,11 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_l1_kernel(WgradParams p) {
     h16x8 gf[4], xf[9];
     auto reads = [&](const char* cur, int s2) {
 #pragma unroll
-        for (int a = 0; a < 4; ++a) gf[a] = trf(cur + go[a] + 4096 * s2, cur + go[a] + 4096 * s2 + 512);
+        for (int a = 0; a < 4; ++a) gf[a] = tr16_frag(cur + go[a] + 4096 * s2, cur + go[a] + 4096 * s2 + 512);
 #pragma unroll
         for (int t = 0; t < 9; ++t) {
             const int off = (t / 3) * L1W_REG * 128 + 4096 * s2;
-            xf[t] = trf(cur + xo[t % 3][0] + off, cur + xo[t % 3][1] + off);
+            xf[t] = tr16_frag(cur + xo[t % 3][0] + off, cur + xo[t % 3][1] + off);
         }
     };
     auto mfmas = [&]() {
@@ -2689,11 +2606,6 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_l1_kernel(WgradParams p) {
                     acc[a][t] = mfma_16x16x32_h16(xf[t], gf[a], acc[a][t]);
                 }
             }
-    };
-    auto bar = [&]() {
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();                 // raw: a __syncthreads() fence would drain the stages in flight
-        __builtin_amdgcn_sched_barrier(0);
     };
 
     // L1W_NBUF stage buffers: stage t + NBUF - 1 is fetched while stage t is computed.  Every iteration issues a
@@ -2731,7 +2643,7 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_l1_kernel(WgradParams p) {
         } else {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
-        bar();
+        pp_barrier();
         int b0 = 0;                                   // buffer of stage t
         for (int t = 0; t < nk; ++t) {
             const int b3 = b0 == 0 ? L1W_NBUF - 1 : b0 - 1;   // buffer of stage t+NBUF-1 (= that of stage t-1)
@@ -2744,7 +2656,7 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_l1_kernel(WgradParams p) {
             mfmas();
             wait_next();
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            bar();
+            pp_barrier();
             b0 = b0 == L1W_NBUF - 1 ? 0 : b0 + 1;
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -2900,8 +2812,7 @@ __global__ __launch_bounds__(64 * WV, 8 / WV) void conv1x1_stream_kernel(GemmPar
     if constexpr (MODE == 3) {
         for (int i = tid; i < N; i += NT) bnp[i] = p.bias ? p.bias[cb + i] : 0.f;
     }
-    const __amdgpu_buffer_rsrc_t ers = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(MODE == 3 && p.res ? p.res : p.x), (short)0, MODE == 3 && p.res ? p.ybytes : 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t ers = buf_rsrc(MODE == 3 && p.res ? p.res : p.x, MODE == 3 && p.res ? p.ybytes : 0);
     __syncthreads();
 
     const long chunk0 = (long)blockIdx.x * cpw;
@@ -3107,7 +3018,7 @@ __global__ __launch_bounds__(64 * WV, 8 / WV) void conv1x1_stream_kernel(GemmPar
         constexpr int ND = UP * K / 8 / (64 * SPL);         // LDS-DMA instructions per wave and unit
         constexpr int EW = MODE != 0 ? UA * NB / 2 : 0;     // epilogue operand loads per wave and unit
         constexpr int SW = UA * NB / 2;                     // output stores per wave and unit
-        const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, (short)0, p.xbytes, 0x00020000);
+        const __amdgpu_buffer_rsrc_t xrs = buf_rsrc(p.x, p.xbytes);
         const int ws = wave % SPL;
         auto dma_unit = [&](int u, int b) {
             char* dst = xs + (b * PXW + pw) * XU;
@@ -3183,7 +3094,7 @@ __global__ __launch_bounds__(64 * WV, 8 / WV) void conv1x1_stream_kernel(GemmPar
                 double s = 0.0, q = 0.0;
 #pragma unroll
                 for (int w = 0; w < PXW; ++w) { s += red[(w * N + c) * 2]; q += red[(w * N + c) * 2 + 1]; }
-                const int rep = (int)(blockIdx.x % SCD_STAT_REPLICAS);
+                const int rep = (int)(blockIdx.x % SCD_STAT_REPLICAS);   // (mirrors stat_replica / stat_slot)
                 atomic_add_f64(p.stats + ((long)rep * 2 + 0) * p.Co + cb + c, s);
                 atomic_add_f64(p.stats + ((long)rep * 2 + 1) * p.Co + cb + c, q);
             }
@@ -3194,17 +3105,6 @@ __global__ __launch_bounds__(64 * WV, 8 / WV) void conv1x1_stream_kernel(GemmPar
 
 SCD_KERNEL_NS_END
 }  // namespace
-
-static int num_cus() {
-    static int n = 0;
-    if (n == 0) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-            n = 256;
-    }
-    return n;
-}
 
 // The tile table of a launch: ntn column tiles per BM pixels, the phases' tiles one after another.  Returns the tiles.
 static int fill_tiles(GemmParams& p, int nphase, const scd_gemm_phase* phases, int BM, int ntn) {
@@ -3620,8 +3520,7 @@ extern "C" int scd_conv_gemm_heads_keep(int dtype, const void* x, const void* w,
     return conv_gemm_launch(dtype, p, 1, &ph, stream);
 }
 
-static void wgrad_tile(int dtype, long M, int Cg, int& tm, int& tn) {
-    (void)dtype; (void)M;
+static void wgrad_tile(int Cg, int& tm, int& tn) {
     if (Cg <= 64) { tm = 64; tn = 256; }
     else { tm = 128; tn = 128; }
 }
@@ -3714,7 +3613,7 @@ extern "C" int scd_conv_wgrad_nsplit2(int dtype, long M, int Ho, int Wo, int Cg,
 extern "C" int scd_conv_wgrad_nsplit(int dtype, long M, int Cg, int T, int Ci) {
     SCD_F16_FWD(scd_conv_wgrad_nsplit, M, Cg, T, Ci);
     int tm, tn;
-    wgrad_tile(dtype, M, Cg, tm, tn);
+    wgrad_tile(Cg, tm, tn);
     const long tiles = (long)cdiv(Cg, tm) * cdiv((long)T * Ci, tn);
     // ~4 waves of two-per-CU workgroups over 256 CUs, >= 1024 pixels per split, fp32 slabs capped at 256 MB
     if (M >= 8 * 1024) {
@@ -3786,7 +3685,7 @@ extern "C" int scd_conv_wgrad(int dtype, const void* g, const void* x, float* ws
         p.cg0 = Cg / win * win;
         p.cgn = Cg % win;
         int BM, BN;
-        wgrad_tile(dtype, M, p.cgn, BM, BN);
+        wgrad_tile(p.cgn, BM, BN);
         p.ntm = cdiv(p.cgn, BM);
         p.ntn = cdiv(p.KK, BN);
         // stages of one row (FASTX 1, Wo % 64 == 0) or of whole rows (FASTX 2, 64 % Wo == 0)
@@ -3795,7 +3694,7 @@ extern "C" int scd_conv_wgrad(int dtype, const void* g, const void* x, float* ws
         SCD_RETURN_LAUNCH();
     }
     int BM, BN;
-    wgrad_tile(dtype, M, Cg, BM, BN);
+    wgrad_tile(Cg, BM, BN);
     p.ntm = cdiv(Cg, BM);
     p.ntn = cdiv(p.KK, BN);
     p.nsplit = nsplit;

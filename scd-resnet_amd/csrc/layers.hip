@@ -3,6 +3,7 @@
 // layout allows.
 #include <algorithm>
 
+#include "gemm_common.h"
 #include "scd_common.h"
 
 namespace {
@@ -402,7 +403,7 @@ __global__ __launch_bounds__(256) void stem_pool_bwd_bn_kernel(const T* dout, co
         const int cc = c / E, e = c - (c / E) * E;
         double a = 0.0;
         for (int t = cc; t < (int)blockDim.x; t += cpp) a += red[stat][t][e];
-        atomic_add_f64(stats + ((long)(blockIdx.x % SCD_STAT_REPLICAS) * 2 + stat) * C + c, a);
+        atomic_add_f64(stat_slot(stats, stat_replica(blockIdx.x), stat, C, c), a);
     }
 }
 
@@ -497,7 +498,7 @@ __global__ __launch_bounds__(256) void stem_pool_bwd_bn_2x2_kernel(const T* dout
         const int cc = c / E, e = c - (c / E) * E;
         double a = 0.0;
         for (int t = cc; t < (int)blockDim.x; t += cpp) a += red[stat][t][e];
-        atomic_add_f64(stats + ((long)(blockIdx.x % SCD_STAT_REPLICAS) * 2 + stat) * C + c, a);
+        atomic_add_f64(stat_slot(stats, stat_replica(blockIdx.x), stat, C, c), a);
     }
 }
 
@@ -1033,9 +1034,9 @@ __global__ __launch_bounds__(256) void heads_sparse_fixup_kernel(T* dx, const T*
             }
         }
         if (bny) {
-            const int rep = s % SCD_STAT_REPLICAS;
-            atomic_add_f64(stats + ((long)rep * 2 + 0) * Cin + ci, (double)dsum);
-            atomic_add_f64(stats + ((long)rep * 2 + 1) * Cin + ci, (double)dsq);
+            const int rep = stat_replica(s);
+            atomic_add_f64(stat_slot(stats, rep, 0, Cin, ci), (double)dsum);
+            atomic_add_f64(stat_slot(stats, rep, 1, Cin, ci), (double)dsq);
         }
     }
 }

@@ -170,13 +170,23 @@ __device__ __forceinline__ void atomic_add_f32(float* p, float v) { unsafeAtomic
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
+// Compute units of the current device (256 when the query fails), asked once per process
+static inline int num_cus() {
+    static int n = 0;
+    if (n == 0) {
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess ||
+            hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
+            n = 256;
+    }
+    return n;
+}
+
 // Workgroups of `kernel` (blockDim `threads`, no dynamic LDS) resident on the whole device at once:
 // grid-stride HBM kernels launch exactly this many, so every workgroup runs in the first (only) round
 // and the grid never has a partial second round.
 static inline int resident_grid(const void* kernel, int threads, size_t dyn_lds = 0) {
-    int dev = 0, cus = 256, per = 1;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-        cus = 256;
+    int per = 1;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kernel, threads, dyn_lds) != hipSuccess || per < 1) per = 1;
-    return per * cus;
+    return per * num_cus();
 }

@@ -8,24 +8,13 @@
 // fp32 64 x 64 partial per split (reduced by scd_wgrad_reduce, T = 1, Ci = 64, cvalid = 49).
 #include <algorithm>
 
+#include "gemm_common.h"
 #include "scd_common.h"
 
 namespace {
 SCD_KERNEL_NS_BEGIN
 
 constexpr int KS = 7, KK = 49, SP = 2, PD = 3, CO = 64;
-
-__device__ __forceinline__ int swz128(int row, int chunk) { return row * 128 + ((chunk ^ (row & 7)) << 4); }
-
-// sum over the 16 lanes of a DPP row (quad butterflies, then the half-row and row mirrors): VALU only, where
-// __shfl_xor costs an LDS permute per step
-__device__ __forceinline__ float stem_row16_sum(float v) {
-    v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x141, 0xF, 0xF, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x140, 0xF, 0xF, true));
-    return v;
-}
 
 // ---- forward: one workgroup = 2 output rows x 128 output columns (256 pixels) of one image
 constexpr int FTW = 128, FTH = 2;
@@ -63,7 +52,7 @@ __global__ __launch_bounds__(256, STEM_FWD_OCC) void stem_conv_fwd_kernel(const 
     // weights: 64 rows x 8 chunks of 16 B
     for (int i = tid; i < CO * 8; i += 256) {
         const int r = i >> 3, c = i & 7;
-        *(uint4*)(Bs + swz128(r, c)) = *(const uint4*)(wpk + r * 64 + c * 8);
+        *(uint4*)(Bs + swz(r, c)) = *(const uint4*)(wpk + r * 64 + c * 8);
     }
     // input patch (zero outside the image): a fixed number of loads per thread from clamped addresses, all in flight
     // at once (a bounds branch around each load made the compiler wait for every one before the next)
@@ -100,7 +89,7 @@ __global__ __launch_bounds__(256, STEM_FWD_OCC) void stem_conv_fwd_kernel(const 
                 const int k = c * 8 + e;
                 v[e] = (h16)(k < KK ? pp[(k / KS) * FROW + ((k % KS) & 1) * FPAR + ((k % KS) >> 1)] : 0.f);
             }
-            *(h16x8*)(As + swz128(tid, c)) = v;
+            *(h16x8*)(As + swz(tid, c)) = v;
         }
     }
     __syncthreads();
@@ -168,7 +157,7 @@ __global__ __launch_bounds__(256, STEM_FWD_OCC) void stem_conv_fwd_kernel(const 
         for (int b = 0; b < 4; ++b)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const float s = stem_row16_sum(csum[b][r]), q = stem_row16_sum(csq[b][r]);
+                const float s = row16_sum(csum[b][r]), q = row16_sum(csq[b][r]);
                 if (l16 == 0) {
                     const int c = b * 16 + lg * 4 + r;
                     red[(wave * CO + c) * 2] = s;
@@ -180,9 +169,9 @@ __global__ __launch_bounds__(256, STEM_FWD_OCC) void stem_conv_fwd_kernel(const 
             double s = 0.0, q = 0.0;
 #pragma unroll
             for (int w = 0; w < 4; ++w) { s += red[(w * CO + tid) * 2]; q += red[(w * CO + tid) * 2 + 1]; }
-            const int rep = bid % SCD_STAT_REPLICAS;
-            atomic_add_f64(stats + ((long)rep * 2 + 0) * CO + tid, s);
-            atomic_add_f64(stats + ((long)rep * 2 + 1) * CO + tid, q);
+            const int rep = stat_replica(bid);
+            atomic_add_f64(stat_slot(stats, rep, 0, CO, tid), s);
+            atomic_add_f64(stat_slot(stats, rep, 1, CO, tid), q);
         }
     }
 }
@@ -192,9 +181,7 @@ __global__ __launch_bounds__(256, STEM_FWD_OCC) void stem_conv_fwd_kernel(const 
 // the [tap][pixel] tile is built transposed so its fragments are plain 16-B reads.
 constexpr int WPX = 64;
 constexpr int WPCOLS = SP * (WPX - 1) + KS + 1;     // 134
-constexpr int DROW = 288;                           // dy stage row stride (128 B of data): conflict-free tr reads
-
-__device__ __forceinline__ int dswz(int row, int byte) { return row * DROW + (byte ^ (((row >> 3) & 1) << 7)); }
+constexpr int DROW = wrow_stride(128);              // dy stage row stride (128 B of data): conflict-free tr reads (wswz)
 
 __global__ __launch_bounds__(256) void stem_conv_wgrad_kernel(const h16* __restrict__ dy, const h16* __restrict__ ybn,
                                                               const float* __restrict__ coef, const float* __restrict__ x,
@@ -221,7 +208,6 @@ __global__ __launch_bounds__(256) void stem_conv_wgrad_kernel(const h16* __restr
     for (int a = 0; a < 2; ++a)
 #pragma unroll
         for (int b = 0; b < 2; ++b) acc[a][b] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    typedef __attribute__((ext_vector_type(8))) short s16x8;
 
     for (long ps = p0; ps < p1; ps += WPX) {
         // stage position: WPX pixels of one output row (Wo % WPX == 0, chunk % WPX == 0)
@@ -249,7 +235,7 @@ __global__ __launch_bounds__(256) void stem_conv_wgrad_kernel(const h16* __restr
                 }
                 v = __builtin_bit_cast(uint4, o8);
             }
-            *(uint4*)(Ds + dswz(r, c * 16)) = v;
+            *(uint4*)(Ds + wswz(r, c * 16, DROW)) = v;
         }
         for (int i = tid; i < KS * WPCOLS; i += 256) {
             const int r = i / WPCOLS, c = i - (i / WPCOLS) * WPCOLS;
@@ -269,7 +255,7 @@ __global__ __launch_bounds__(256) void stem_conv_wgrad_kernel(const h16* __restr
                     const int px = pq * 16 + h * 8 + e;
                     v[e] = (h16)(k < KK ? patch[kh * WPCOLS + SP * px + kw] : 0.f);
                 }
-                *(h16x8*)(Cs + swz128(k, pq * 2 + h)) = v;
+                *(h16x8*)(Cs + swz(k, pq * 2 + h)) = v;
             }
         }
         __syncthreads();
@@ -280,14 +266,11 @@ __global__ __launch_bounds__(256) void stem_conv_wgrad_kernel(const h16* __restr
             h16x8 tf[2], df[2];
 #pragma unroll
             for (int b = 0; b < 2; ++b)
-                tf[b] = *(const h16x8*)(Cs + swz128(wn * 32 + b * 16 + l16, s * 4 + lg));
+                tf[b] = *(const h16x8*)(Cs + swz(wn * 32 + b * 16 + l16, s * 4 + lg));
 #pragma unroll
             for (int a = 0; a < 2; ++a) {
                 const int cb = (wm * 32 + a * 16 + 4 * pp) * 2;
-                s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(Ds + dswz(r0, cb)));
-                s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(Ds + dswz(r0 + 4, cb)));
-                s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-                df[a] = __builtin_bit_cast(h16x8, v);
+                df[a] = tr16_frag(Ds + wswz(r0, cb, DROW), Ds + wswz(r0 + 4, cb, DROW));
             }
 #pragma unroll
             for (int a = 0; a < 2; ++a)
@@ -352,7 +335,6 @@ __global__ __launch_bounds__(256, 2) void stem_bwd_fused_kernel(
     const int gpr = Wo / BTW;                        // column groups per conv row pair
     const int tpi = Hp * gpr;
     const int bl = tid >> 3, ch = tid & 7;           // this thread's 2x2 block of the tile and channel chunk
-    typedef __attribute__((ext_vector_type(8))) short s16x8;
 
     float s1[8], s2[8];
 #pragma unroll
@@ -459,7 +441,7 @@ __global__ __launch_bounds__(256, 2) void stem_bwd_fused_kernel(
                     s1[e] += r;
                     s2[e] += r * (v[e] - mu[e]) * is[e];
                 }
-                *(h16x8*)(Ds + a * DT + dswz(2 * bl + b, ch * 16)) = o8;
+                *(h16x8*)(Ds + a * DT + wswz(2 * bl + b, ch * 16, DROW)) = o8;
             }
 #pragma unroll
         for (int q = 0; q < (BPROWS * WPCOLS + 255) / 256; ++q) {
@@ -490,7 +472,7 @@ __global__ __launch_bounds__(256, 2) void stem_bwd_fused_kernel(
                         const float pv = patch[(2 * a + kh) * PROW + (kw & 1) * PPAR + px + (kw >> 1)];
                         v[e] = (h16)(k < KK ? pv : kfill);
                     }
-                    *(h16x8*)(Cs + a * CT + swz128(k, pq * 2 + h)) = v;
+                    *(h16x8*)(Cs + a * CT + swz(k, pq * 2 + h)) = v;
                 }
         }
         __syncthreads();
@@ -503,15 +485,12 @@ __global__ __launch_bounds__(256, 2) void stem_bwd_fused_kernel(
                 const int r0 = 32 * s + 8 * lg + q4;
                 h16x8 tf[2], df[2], gf[2];
 #pragma unroll
-                for (int b = 0; b < 2; ++b) tf[b] = *(const h16x8*)(C + swz128(wn * 32 + b * 16 + l16, s * 4 + lg));
+                for (int b = 0; b < 2; ++b) tf[b] = *(const h16x8*)(C + swz(wn * 32 + b * 16 + l16, s * 4 + lg));
 #pragma unroll
                 for (int i = 0; i < 2; ++i) {
-                    gf[i] = *(const h16x8*)(C + swz128(wm * 32 + i * 16 + l16, s * 4 + lg));
+                    gf[i] = *(const h16x8*)(C + swz(wm * 32 + i * 16 + l16, s * 4 + lg));
                     const int cb = (wm * 32 + i * 16 + 4 * pp) * 2;
-                    s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(D + dswz(r0, cb)));
-                    s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(D + dswz(r0 + 4, cb)));
-                    s16x8 v8 = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-                    df[i] = __builtin_bit_cast(h16x8, v8);
+                    df[i] = tr16_frag(D + wswz(r0, cb, DROW), D + wswz(r0 + 4, cb, DROW));
                 }
 #pragma unroll
                 for (int i = 0; i < 2; ++i)
@@ -543,7 +522,7 @@ __global__ __launch_bounds__(256, 2) void stem_bwd_fused_kernel(
         const int cc = c / 8, e = c - (c / 8) * 8;
         double acc = 0.0;
         for (int t = cc; t < 256; t += 8) acc += red[(stat * 256 + t) * 9 + e];
-        atomic_add_f64(stats + ((long)(blockIdx.x % SCD_STAT_REPLICAS) * 2 + stat) * CO + c, acc);
+        atomic_add_f64(stat_slot(stats, stat_replica(blockIdx.x), stat, CO, c), acc);
     }
 }
 
@@ -664,9 +643,6 @@ extern "C" int scd_stem_conv_wgrad_nsplit(long M) {
 }
 
 extern "C" int scd_stem_bwd_nsplit(void) {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-        cus = 256;
-    return 2 * cus;
+    return 2 * num_cus();
 }
 #endif  // !SCD_F16_BUILD
