@@ -13,9 +13,10 @@
 // kernel holds 2 x 216 of the 512 VGPRs per SIMD lane (one 8-wave workgroup per CU), so a wave that needs 88 could
 // not start on any CU until those workgroups retire (in the step the deconv2 BN backward apply then waited out the
 // whole deconv3 weight gradient)
-// vectors in flight per thread in bn_bwd_apply_kernel (80 VGPRs at 2, no spill): beside the weight-gradient stream's
-// one-workgroup-per-CU GEMM a CU holds one or two of its waves per SIMD, so the bytes each wave keeps in flight set
-// its bandwidth there (75 VGPRs at 2 in both 16-bit builds since the loop is specialised per mask kind)
+// vectors in flight per thread in the one-layer bn_bwd_apply_kernel (80 VGPRs at 2, no spill): beside the
+// weight-gradient stream's one-workgroup-per-CU GEMM a CU holds one or two of its waves per SIMD, so the bytes each
+// wave keeps in flight set its bandwidth there (75 VGPRs at 2 in both 16-bit builds since the loop is specialised per
+// mask kind)
 #ifndef BN_APPLY_U
 #define BN_APPLY_U 2
 #endif
@@ -119,43 +120,133 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const T* y, T* out, int C
     }
 }
 
-// Per-channel Σdz and Σdz·x̂ over rows (dz = dout masked by relu(mask) > 0).  A 256-thread block owns
-// rows [r0, r1): thread = (row lane rsub, 16-B channel chunk ch); 4 rows per step are loaded before
-// any is used (4 x 3 independent 16-B loads in flight per thread); the block's partials are folded
-// over row lanes in LDS by all threads and added to one fp64 replica slot per channel.
-template <typename T>
-__global__ __launch_bounds__(256, BN_EW_WAVES) void bn_bwd_reduce_kernel(const T* dout, const T* mask, const T* y,
-                                                            const float* rsc, const float* rsh,
-                                                            const float* mean, const float* invstd, int C, int ld,
-                                                            unsigned rows, unsigned rows_per_block, double* stats) {
+// ---- BatchNorm backward, for one layer (NL = 1) or for the two layers behind one residual join (NL = 2: BasicBlock /
+// Bottleneck bn2|bn3 + downsample BN, residuals.py:110-120, 158-165; CornerPool branchMergeBn + shortcutBn,
+// cornerNetCPool.py:117-122).  Both layers of a pair take the same gradient dout through the same stored ReLU mask, so
+// one pass reads dout and the mask once for both.  The layer count is a template parameter of the same kernels: per
+// element and per thread a pair pass computes what two single passes with that mask compute.
+//
+// Kernel arguments.  NL = 1 has the three mask kinds (0: none, 1: the stored activation `mask`, 2: BN+ReLU recomputed
+// from y with rsc / rsh); NL = 2 has kind 1 only (the host rejects a null mask).
+template <typename T, int NL> struct BwdReduceArgs;
+template <typename T> struct BwdReduceArgs<T, 1> {
+    const T *dout, *mask, *y[1];
+    const float *rsc, *rsh, *mi[2];                 // mi: mean, invstd
+    int C, ld;
+    unsigned rows, rows_per_block;
+    double* stats[1];
+};
+template <typename T> struct BwdReduceArgs<T, 2> {
+    const T *dout, *mask, *y[2];
+    const float* mi[4];                             // mean_a, invstd_a, mean_b, invstd_b
+    int C, ld;
+    unsigned rows, rows_per_block;
+    double* stats[2];
+};
+template <typename T, int NL> struct BwdApplyArgs;
+template <typename T> struct BwdApplyArgs<T, 1> {
+    const T *dout, *mask, *y[1];
+    const float *rsc, *rsh, *coef[1];
+    int C;
+    unsigned nvec;
+    T *dy[1], *dz;                                  // dz: optional, the masked gradient
+};
+template <typename T> struct BwdApplyArgs<T, 2> {
+    const T *dout, *mask, *y[2];
+    const float* coef[2];
+    int C;
+    unsigned nvec;
+    T* dy[2];
+};
+// per-channel arrays bn_bwd_apply_kernel stages: 3 coefficients per layer, and rsc, rsh of the one layer
+constexpr int bwd_apply_nsrc(int NL) { return NL == 1 ? 5 : 6; }
+
+// one step's operands as loaded, packed (16 B each) until used: dout, the stored activation (mask kind 1), NL layers' y
+template <int NL> struct BwdRaw { uint4 d, m, y[NL]; };
+template <int MK, typename T, int NL>
+__device__ __forceinline__ void load_bwd_raw(const T* dout, const T* mask, const T* const (&y)[NL], size_t i,
+                                             BwdRaw<NL>& raw) {
+    raw.d = *(const uint4*)(dout + i);
+#pragma unroll
+    for (int l = 0; l < NL; ++l) raw.y[l] = *(const uint4*)(y[l] + i);
+    raw.m = MK == 1 ? *(const uint4*)(mask + i) : make_uint4(0, 0, 0, 0);
+}
+
+// The loop of the backward kernels over steps i, i + stride, .. < end: U steps are loaded before any is used (U x the
+// step's 16-B loads in flight per thread), then a ragged tail one step at a time.
+template <int U, typename Raw, typename Load, typename Use>
+__device__ __forceinline__ void loads_ahead_loop(unsigned i, unsigned end, unsigned stride, Load load, Use use) {
+    for (; i + (U - 1) * stride < end; i += U * stride) {
+        Raw raw[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) load(i + u * stride, raw[u]);
+#pragma unroll
+        for (int u = 0; u < U; ++u) use(i + u * stride, raw[u]);
+    }
+    if constexpr (U > 1) {
+        for (; i < end; i += stride) {
+            Raw raw;
+            load(i, raw);
+            use(i, raw);
+        }
+    }
+}
+// one loop per mask kind: with the kind a runtime test inside the element loop the compiler built the loop from
+// per-element branch regions (8 per vector)
+template <int NL, typename Args, typename Run>
+__device__ __forceinline__ void per_mask_kind(const Args& a, Run run) {
+    if constexpr (NL == 2) {
+        run(std::integral_constant<int, 1>{});
+    } else {
+        if (a.mask) run(std::integral_constant<int, 1>{});
+        else if (a.rsc) run(std::integral_constant<int, 2>{});
+        else run(std::integral_constant<int, 0>{});
+    }
+}
+
+// Per-channel Σdz and, per layer, Σdz·x̂ over rows (dz = dout masked by relu(mask) > 0).  A 256-thread block owns
+// rows [r0, r1): thread = (row lane rsub, 16-B channel chunk ch); BN_BWD_U rows per step are loaded before any is
+// used; the block's partials are folded over row lanes in LDS by all threads and added to one fp64 replica slot per
+// channel (Σdz to every layer's).
+template <typename T, int NL>
+__global__ __launch_bounds__(256, BN_EW_WAVES) void bn_bwd_reduce_kernel(BwdReduceArgs<T, NL> a) {
     constexpr int E = Vec16<T>::N;
-    constexpr int U = BN_BWD_U;
     constexpr int nt = 256;
+    const int C = a.C, ld = a.ld;
     const int cpr = C / E;                     // chunks per row of this channel slice (divides 256)
     const int rpi = nt / cpr;                  // row lanes
     const int tid = threadIdx.x;
     const int ch = tid % cpr;
     const int rsub = tid / cpr;
-    const unsigned r0 = blockIdx.x * rows_per_block;
-    const unsigned r1 = min(rows, r0 + rows_per_block);
+    const unsigned r0 = blockIdx.x * a.rows_per_block;
+    const unsigned r1 = min(a.rows, r0 + a.rows_per_block);
     __shared__ float red[2 * nt * E];
-    extern __shared__ __attribute__((aligned(16))) float sp[];        // 4 x C floats (dynamic LDS)     // mean, invstd, rsc, rsh
+    // 4 x C floats (dynamic LDS): mean, invstd, rsc, rsh | mean_a, invstd_a, mean_b, invstd_b
+    extern __shared__ __attribute__((aligned(16))) float sp[];
     {
-        const float* src[4] = {mean, invstd, rsc, rsh};
+        const float* src[4] = {a.mi[0], a.mi[1]};
+        if constexpr (NL == 1) { src[2] = a.rsc; src[3] = a.rsh; }
+        else { src[2] = a.mi[2]; src[3] = a.mi[3]; }
         stage_params(sp, src, 4, 0, C);
     }
-    float s[E], q[E];
+    float s[E], q[NL][E];
 #pragma unroll
-    for (int e = 0; e < E; ++e) { s[e] = 0.f; q[e] = 0.f; }
-    // one loop per mask kind (0: none, 1: the stored activation, 2: BN+ReLU recomputed from y), as in
-    // bn_bwd_apply_kernel: no per-element branch regions
-    auto run = [&](auto kind) {
+    for (int e = 0; e < E; ++e) {
+        s[e] = 0.f;
+#pragma unroll
+        for (int l = 0; l < NL; ++l) q[l][e] = 0.f;
+    }
+    per_mask_kind<NL>(a, [&](auto kind) {
         constexpr int MK = decltype(kind)::value;
-        auto acc_raw = [&](const uint4& rd, const uint4& ry, const uint4& rm) {
-            float d[E], yv[E], mk[E], mu[E], is[E], ka[E], kb[E];
-            Vec16<T>::load(&rd, d);
-            Vec16<T>::load(&ry, yv);
-            if constexpr (MK == 1) Vec16<T>::load(&rm, mk);
+        auto load = [&](unsigned r, BwdRaw<NL>& raw) {
+            load_bwd_raw<MK>(a.dout, a.mask, a.y, r * (unsigned)ld + ch * E, raw);
+        };
+        auto acc = [&](unsigned, const BwdRaw<NL>& raw) {
+            float d[E], yv[NL][E], mk[E], mu[E], is[E], ka[E], kb[E];
+            Vec16<T>::load(&raw.d, d);
+#pragma unroll
+            for (int l = 0; l < NL; ++l) Vec16<T>::load(&raw.y[l], yv[l]);
+            if constexpr (MK == 1) Vec16<T>::load(&raw.m, mk);
             lds_params<E>(sp, ch * E, mu);
             lds_params<E>(sp, C + ch * E, is);
             if constexpr (MK == 2) { lds_params<E>(sp, 2 * C + ch * E, ka); lds_params<E>(sp, 3 * C + ch * E, kb); }
@@ -163,280 +254,117 @@ __global__ __launch_bounds__(256, BN_EW_WAVES) void bn_bwd_reduce_kernel(const T
             for (int e = 0; e < E; ++e) {
                 bool off = false;
                 if constexpr (MK == 1) off = !(mk[e] > 0.f);
-                if constexpr (MK == 2) off = !(yv[e] * ka[e] + kb[e] > 0.f);
-                const float dz = off ? 0.f : d[e];
-                s[e] += dz;
-                q[e] += dz * (yv[e] - mu[e]) * is[e];
+                if constexpr (MK == 2) off = !(yv[0][e] * ka[e] + kb[e] > 0.f);
+                d[e] = off ? 0.f : d[e];
+                s[e] += d[e];
+                q[0][e] += d[e] * (yv[0][e] - mu[e]) * is[e];
+            }
+            if constexpr (NL == 2) {
+                lds_params<E>(sp, 2 * C + ch * E, mu);
+                lds_params<E>(sp, 3 * C + ch * E, is);
+#pragma unroll
+                for (int e = 0; e < E; ++e) q[1][e] += d[e] * (yv[1][e] - mu[e]) * is[e];
             }
         };
-        unsigned r = r0 + rsub;
-        for (; r + (U - 1) * rpi < r1; r += U * rpi) {
-            uint4 rd[U], ry[U], rm[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const unsigned i = (r + u * rpi) * (unsigned)ld + ch * E;
-                rd[u] = *(const uint4*)(dout + i);
-                ry[u] = *(const uint4*)(y + i);
-                rm[u] = MK == 1 ? *(const uint4*)(mask + i) : make_uint4(0, 0, 0, 0);
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) acc_raw(rd[u], ry[u], rm[u]);
-        }
-        for (; r < r1; r += rpi) {
-            const unsigned i = r * (unsigned)ld + ch * E;
-            const uint4 rd = *(const uint4*)(dout + i), ry = *(const uint4*)(y + i);
-            const uint4 rm = MK == 1 ? *(const uint4*)(mask + i) : make_uint4(0, 0, 0, 0);
-            acc_raw(rd, ry, rm);
-        }
-    };
-    if (mask) run(std::integral_constant<int, 1>{});
-    else if (rsc) run(std::integral_constant<int, 2>{});
-    else run(std::integral_constant<int, 0>{});
-    // red[stat][rsub][channel]
+        loads_ahead_loop<BN_BWD_U, BwdRaw<NL>>(r0 + rsub, r1, rpi, load, acc);
+    });
+    const int rep = (int)(blockIdx.x % SCD_STAT_REPLICAS);   // (mirrors stat_replica / stat_slot, gemm_common.h)
+    // red[stat][rsub][channel].  Pass 1: sum dz (every layer's) and layer 0's sum dz*xhat; pass 2: layer 1's
 #pragma unroll
     for (int e = 0; e < E; ++e) {
         red[rsub * C + ch * E + e] = s[e];
-        red[nt * E + rsub * C + ch * E + e] = q[e];
+        red[nt * E + rsub * C + ch * E + e] = q[0][e];
     }
     __syncthreads();
-    const int rep = (int)(blockIdx.x % SCD_STAT_REPLICAS);   // (mirrors stat_replica / stat_slot, gemm_common.h)
     for (int c = tid; c < C; c += nt) {
         double ss = 0.0, qq = 0.0;
         for (int k = 0; k < rpi; ++k) {
             ss += red[k * C + c];
             qq += red[nt * E + k * C + c];
         }
-        atomic_add_f64(stats + ((long)rep * 2 + 0) * ld + c, ss);
-        atomic_add_f64(stats + ((long)rep * 2 + 1) * ld + c, qq);
+        atomic_add_f64(a.stats[0] + ((long)rep * 2 + 0) * ld + c, ss);
+        atomic_add_f64(a.stats[0] + ((long)rep * 2 + 1) * ld + c, qq);
+        if constexpr (NL == 2) atomic_add_f64(a.stats[1] + ((long)rep * 2 + 0) * ld + c, ss);
+    }
+    if constexpr (NL == 2) {
+        __syncthreads();
+#pragma unroll
+        for (int e = 0; e < E; ++e) red[nt * E + rsub * C + ch * E + e] = q[1][e];
+        __syncthreads();
+        for (int c = tid; c < C; c += nt) {
+            double qq = 0.0;
+            for (int k = 0; k < rpi; ++k) qq += red[nt * E + k * C + c];
+            atomic_add_f64(a.stats[1] + ((long)rep * 2 + 1) * ld + c, qq);
+        }
     }
 }
 
-template <typename T>
-__global__ __launch_bounds__(256, BN_EW_WAVES) void bn_bwd_apply_kernel(const T* dout, const T* mask, const T* y, const float* rsc,
-                                                           const float* rsh, const float* coef, int C, unsigned nvec,
-                                                           T* dy, T* dz_out) {
+// dy = a*dz + b*y + c per layer (and dz itself, NL = 1 with a.dz).  Vectors in flight, kept packed until used:
+// BN_APPLY_U for one layer, BN_BWD_U for a pair (twice the operands per step): <= 80 VGPRs, so the kernel's waves fit
+// beside a one-workgroup-per-CU GEMM of the weight-gradient stream (2 x 216 of the 512 VGPRs per lane) instead of
+// waiting for its workgroups to retire
+template <typename T, int NL>
+__global__ __launch_bounds__(256, BN_EW_WAVES) void bn_bwd_apply_kernel(BwdApplyArgs<T, NL> a) {
     constexpr int E = Vec16<T>::N;
-    // BN_APPLY_U vectors in flight, kept packed (16 B each) until used: <= 80 VGPRs, so the kernel's waves fit beside
-    // a one-workgroup-per-CU GEMM of the weight-gradient stream (2 x 216 of the 512 VGPRs per lane) instead of
-    // waiting for its workgroups to retire
-    constexpr int U = BN_APPLY_U;
-    // fixed channel chunk per thread (see bn_apply_kernel): coefficients in registers
+    constexpr int U = NL == 1 ? BN_APPLY_U : BN_BWD_U;
+    constexpr int NS = bwd_apply_nsrc(NL);
+    // fixed channel chunk per thread (see bn_apply_kernel)
+    const int C = a.C;
     const unsigned cpr = (unsigned)C / E;
     const unsigned v0 = blockIdx.x * blockDim.x + threadIdx.x;
     const unsigned stride = gridDim.x * blockDim.x;
     const int c0 = (int)(v0 % cpr) * E;
-    extern __shared__ __attribute__((aligned(16))) float sp[];        // 5 x W floats (dynamic LDS): coef a, b, c, rsc, rsh
+    // NS x W floats (dynamic LDS): coef a, b, c, rsc, rsh | coef_a a, b, c, coef_b a, b, c
+    extern __shared__ __attribute__((aligned(16))) float sp[];
     int cb, W;
     chan_window(C, E, cb, W);
-    {
-        const float* src[5] = {coef, coef + C, coef + 2 * C, rsc, rsh};
-        stage_params(sp, src, 5, cb, W);
+    if constexpr (NL == 1) {
+        const float* src[NS] = {a.coef[0], a.coef[0] + C, a.coef[0] + 2 * C, a.rsc, a.rsh};
+        stage_params(sp, src, NS, cb, W);
+    } else {
+        const float* src[NS] = {a.coef[0], a.coef[0] + C, a.coef[0] + 2 * C,
+                                a.coef[1], a.coef[1] + C, a.coef[1] + 2 * C};
+        stage_params(sp, src, NS, cb, W);
     }
     const int cl = c0 - cb;
-    // raw 16-B vectors -> dz (masked gradient) and dy, stored.  One loop per mask kind (0: none, 1: the stored
-    // activation, 2: BN+ReLU recomputed from y): with the kind a runtime test inside the element loop the compiler
-    // built the loop from per-element branch regions (8 per vector)
-    auto run = [&](auto kind) {
+    per_mask_kind<NL>(a, [&](auto kind) {
         constexpr int MK = decltype(kind)::value;
-        auto body = [&](size_t i, const uint4& rd, const uint4& ry, const uint4& rm) {
-            float d[E], yv[E], mk[E], ca[E], cq[E], cc[E], ka[E], kb[E];
-            Vec16<T>::load(&rd, d);
-            Vec16<T>::load(&ry, yv);
-            if constexpr (MK == 1) Vec16<T>::load(&rm, mk);
-            lds_params<E>(sp, cl, ca);
-            lds_params<E>(sp, W + cl, cq);
-            lds_params<E>(sp, 2 * W + cl, cc);
+        auto load = [&](unsigned v, BwdRaw<NL>& raw) { load_bwd_raw<MK>(a.dout, a.mask, a.y, (size_t)v * E, raw); };
+        // raw 16-B vectors -> dz (masked gradient) and dy, stored
+        auto body = [&](unsigned v, const BwdRaw<NL>& raw) {
+            const size_t i = (size_t)v * E;
+            float d[E], yv[NL][E], mk[E], k0[E], k1[E], k2[E], ka[E], kb[E];
+            Vec16<T>::load(&raw.d, d);
+#pragma unroll
+            for (int l = 0; l < NL; ++l) Vec16<T>::load(&raw.y[l], yv[l]);
+            if constexpr (MK == 1) Vec16<T>::load(&raw.m, mk);
+            lds_params<E>(sp, cl, k0);
+            lds_params<E>(sp, W + cl, k1);
+            lds_params<E>(sp, 2 * W + cl, k2);
             if constexpr (MK == 2) { lds_params<E>(sp, 3 * W + cl, ka); lds_params<E>(sp, 4 * W + cl, kb); }
 #pragma unroll
             for (int e = 0; e < E; ++e) {
                 bool off = false;
                 if constexpr (MK == 1) off = !(mk[e] > 0.f);
-                if constexpr (MK == 2) off = !(yv[e] * ka[e] + kb[e] > 0.f);
-                const float dz = off ? 0.f : d[e];
-                d[e] = dz;
-                yv[e] = ca[e] * dz + cq[e] * yv[e] + cc[e];
+                if constexpr (MK == 2) off = !(yv[0][e] * ka[e] + kb[e] > 0.f);
+                d[e] = off ? 0.f : d[e];
+                yv[0][e] = k0[e] * d[e] + k1[e] * yv[0][e] + k2[e];
             }
-            Vec16<T>::store(dy + i, yv);
-            if (dz_out) Vec16<T>::store(dz_out + i, d);
+            if constexpr (NL == 2) {
+                lds_params<E>(sp, 3 * W + cl, k0);
+                lds_params<E>(sp, 4 * W + cl, k1);
+                lds_params<E>(sp, 5 * W + cl, k2);
+#pragma unroll
+                for (int e = 0; e < E; ++e) yv[1][e] = k0[e] * d[e] + k1[e] * yv[1][e] + k2[e];
+            }
+#pragma unroll
+            for (int l = 0; l < NL; ++l) Vec16<T>::store(a.dy[l] + i, yv[l]);
+            if constexpr (NL == 1) {
+                if (a.dz) Vec16<T>::store(a.dz + i, d);
+            }
         };
-        unsigned v = v0;
-        for (; v + (U - 1) * stride < nvec; v += U * stride) {
-            uint4 rd[U], ry[U], rm[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const size_t i = (size_t)(v + u * stride) * E;
-                rd[u] = *(const uint4*)(dout + i);
-                ry[u] = *(const uint4*)(y + i);
-                rm[u] = MK == 1 ? *(const uint4*)(mask + i) : make_uint4(0, 0, 0, 0);
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) body((size_t)(v + u * stride) * E, rd[u], ry[u], rm[u]);
-        }
-        for (; v < nvec; v += stride) {
-            const size_t i = (size_t)v * E;
-            const uint4 rd = *(const uint4*)(dout + i), ry = *(const uint4*)(y + i);
-            const uint4 rm = MK == 1 ? *(const uint4*)(mask + i) : make_uint4(0, 0, 0, 0);
-            body(i, rd, ry, rm);
-        }
-    };
-    if (mask) run(std::integral_constant<int, 1>{});
-    else if (rsc) run(std::integral_constant<int, 2>{});
-    else run(std::integral_constant<int, 0>{});
-}
-
-// ---- two BN layers behind one residual join (BasicBlock / Bottleneck bn2|bn3 + downsample BN, residuals.py:
-// 110-120, 158-165; CornerPool branchMergeBn + shortcutBn, cornerNetCPool.py:117-122): both take the same gradient
-// dout through the same ReLU mask, so one pass reads dout and the mask once for both.  Per element and per thread the
-// arithmetic is that of bn_bwd_reduce_kernel / bn_bwd_apply_kernel with a mask (no BN+ReLU recompute).
-template <typename T>
-__global__ __launch_bounds__(256, BN_EW_WAVES) void bn_bwd_reduce2_kernel(const T* dout, const T* mask, const T* ya, const T* yb,
-                                                             const float* mean_a, const float* invstd_a,
-                                                             const float* mean_b, const float* invstd_b, int C, int ld,
-                                                             unsigned rows, unsigned rows_per_block, double* stats_a,
-                                                             double* stats_b) {
-    constexpr int E = Vec16<T>::N;
-    constexpr int U = BN_BWD_U;
-    constexpr int nt = 256;
-    const int cpr = C / E;
-    const int rpi = nt / cpr;
-    const int tid = threadIdx.x;
-    const int ch = tid % cpr;
-    const int rsub = tid / cpr;
-    const unsigned r0 = blockIdx.x * rows_per_block;
-    const unsigned r1 = min(rows, r0 + rows_per_block);
-    __shared__ float red[2 * nt * E];
-    extern __shared__ __attribute__((aligned(16))) float sp[];        // 4 x C floats (dynamic LDS)     // mean_a, invstd_a, mean_b, invstd_b
-    {
-        const float* src[4] = {mean_a, invstd_a, mean_b, invstd_b};
-        stage_params(sp, src, 4, 0, C);
-    }
-    float s[E], qa[E], qb[E];
-#pragma unroll
-    for (int e = 0; e < E; ++e) { s[e] = 0.f; qa[e] = 0.f; qb[e] = 0.f; }
-    auto acc_raw = [&](const uint4& rd, const uint4& rm, const uint4& ra, const uint4& rb) {
-        float d[E], mk[E], va[E], vb[E], mu[E], is[E];
-        Vec16<T>::load(&rd, d);
-        Vec16<T>::load(&rm, mk);
-        Vec16<T>::load(&ra, va);
-        Vec16<T>::load(&rb, vb);
-#pragma unroll
-        for (int e = 0; e < E; ++e) d[e] = !(mk[e] > 0.f) ? 0.f : d[e];
-        lds_params<E>(sp, ch * E, mu);
-        lds_params<E>(sp, C + ch * E, is);
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-            s[e] += d[e];
-            qa[e] += d[e] * (va[e] - mu[e]) * is[e];
-        }
-        lds_params<E>(sp, 2 * C + ch * E, mu);
-        lds_params<E>(sp, 3 * C + ch * E, is);
-#pragma unroll
-        for (int e = 0; e < E; ++e) qb[e] += d[e] * (vb[e] - mu[e]) * is[e];
-    };
-    unsigned r = r0 + rsub;
-    for (; r + (U - 1) * rpi < r1; r += U * rpi) {
-        uint4 rd[U], rm[U], ra[U], rb[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const unsigned i = (r + u * rpi) * (unsigned)ld + ch * E;
-            rd[u] = *(const uint4*)(dout + i);
-            rm[u] = *(const uint4*)(mask + i);
-            ra[u] = *(const uint4*)(ya + i);
-            rb[u] = *(const uint4*)(yb + i);
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) acc_raw(rd[u], rm[u], ra[u], rb[u]);
-    }
-    for (; r < r1; r += rpi) {
-        const unsigned i = r * (unsigned)ld + ch * E;
-        acc_raw(*(const uint4*)(dout + i), *(const uint4*)(mask + i), *(const uint4*)(ya + i), *(const uint4*)(yb + i));
-    }
-    const int rep = (int)(blockIdx.x % SCD_STAT_REPLICAS);   // (mirrors stat_replica / stat_slot, gemm_common.h)
-    // pass 1: sum dz (both layers) and layer a's sum dz*xhat; pass 2: layer b's
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-        red[rsub * C + ch * E + e] = s[e];
-        red[nt * E + rsub * C + ch * E + e] = qa[e];
-    }
-    __syncthreads();
-    for (int c = tid; c < C; c += nt) {
-        double ss = 0.0, qq = 0.0;
-        for (int k = 0; k < rpi; ++k) {
-            ss += red[k * C + c];
-            qq += red[nt * E + k * C + c];
-        }
-        atomic_add_f64(stats_a + ((long)rep * 2 + 0) * ld + c, ss);
-        atomic_add_f64(stats_a + ((long)rep * 2 + 1) * ld + c, qq);
-        atomic_add_f64(stats_b + ((long)rep * 2 + 0) * ld + c, ss);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int e = 0; e < E; ++e) red[nt * E + rsub * C + ch * E + e] = qb[e];
-    __syncthreads();
-    for (int c = tid; c < C; c += nt) {
-        double qq = 0.0;
-        for (int k = 0; k < rpi; ++k) qq += red[nt * E + k * C + c];
-        atomic_add_f64(stats_b + ((long)rep * 2 + 1) * ld + c, qq);
-    }
-}
-
-template <typename T>
-__global__ __launch_bounds__(256, BN_EW_WAVES) void bn_bwd_apply2_kernel(const T* dout, const T* mask, const T* ya, const T* yb,
-                                                            const float* coef_a, const float* coef_b, int C,
-                                                            unsigned nvec, T* dya, T* dyb) {
-    constexpr int E = Vec16<T>::N;
-    constexpr int U = BN_BWD_U;
-    const unsigned cpr = (unsigned)C / E;
-    const unsigned v0 = blockIdx.x * blockDim.x + threadIdx.x;
-    const unsigned stride = gridDim.x * blockDim.x;
-    const int c0 = (int)(v0 % cpr) * E;
-    extern __shared__ __attribute__((aligned(16))) float sp[];        // 6 x W floats (dynamic LDS): coef_a a, b, c, coef_b a, b, c
-    int cb, W;
-    chan_window(C, E, cb, W);
-    {
-        const float* src[6] = {coef_a, coef_a + C, coef_a + 2 * C, coef_b, coef_b + C, coef_b + 2 * C};
-        stage_params(sp, src, 6, cb, W);
-    }
-    const int cl = c0 - cb;
-    auto body = [&](size_t i, const uint4& rd, const uint4& rm, const uint4& ra, const uint4& rb) {
-        float d[E], mk[E], va[E], vb[E], k0[E], k1[E], k2[E];
-        Vec16<T>::load(&rd, d);
-        Vec16<T>::load(&rm, mk);
-        Vec16<T>::load(&ra, va);
-        Vec16<T>::load(&rb, vb);
-#pragma unroll
-        for (int e = 0; e < E; ++e) d[e] = !(mk[e] > 0.f) ? 0.f : d[e];
-        lds_params<E>(sp, cl, k0);
-        lds_params<E>(sp, W + cl, k1);
-        lds_params<E>(sp, 2 * W + cl, k2);
-#pragma unroll
-        for (int e = 0; e < E; ++e) va[e] = k0[e] * d[e] + k1[e] * va[e] + k2[e];
-        lds_params<E>(sp, 3 * W + cl, k0);
-        lds_params<E>(sp, 4 * W + cl, k1);
-        lds_params<E>(sp, 5 * W + cl, k2);
-#pragma unroll
-        for (int e = 0; e < E; ++e) vb[e] = k0[e] * d[e] + k1[e] * vb[e] + k2[e];
-        Vec16<T>::store(dya + i, va);
-        Vec16<T>::store(dyb + i, vb);
-    };
-    unsigned v = v0;
-    for (; v + (U - 1) * stride < nvec; v += U * stride) {
-        uint4 rd[U], rm[U], ra[U], rb[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const size_t i = (size_t)(v + u * stride) * E;
-            rd[u] = *(const uint4*)(dout + i);
-            rm[u] = *(const uint4*)(mask + i);
-            ra[u] = *(const uint4*)(ya + i);
-            rb[u] = *(const uint4*)(yb + i);
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) body((size_t)(v + u * stride) * E, rd[u], rm[u], ra[u], rb[u]);
-    }
-    for (; v < nvec; v += stride) {
-        const size_t i = (size_t)v * E;
-        body(i, *(const uint4*)(dout + i), *(const uint4*)(mask + i), *(const uint4*)(ya + i), *(const uint4*)(yb + i));
-    }
+        loads_ahead_loop<U, BwdRaw<NL>>(v0, a.nvec, stride, load, body);
+    });
 }
 
 // elementwise BN kernels keep one channel chunk per thread: the grid stride (grid * 256 threads) must be a
@@ -458,6 +386,56 @@ inline int ew_resident(size_t lds) {
     const size_t k = std::min<size_t>(lds / 16, EW_LDS_MAX / 16);
     if (!cache[k]) cache[k] = resident_grid((const void*)Kernel, 256, lds);
     return cache[k];
+}
+
+// The backward reduce of a.C channels over total / a.C rows (a.ld, rows and rows_per_block are filled in here).  Rows
+// wider than 256 chunks run as channel slices of 256 chunks (ld = the full row).  One round of resident blocks (at
+// most), at least 8 rows per row lane; the grid is sized from the residency of the NL = 1 kernel for either layer
+// count, so a pair pass partitions the rows, and with them every thread's partial sums, like two single passes.
+template <typename T, int NL>
+int launch_bwd_reduce(BwdReduceArgs<T, NL> a, long total, void* stream) {
+    constexpr int E = 16 / sizeof(T);
+    const int C = a.C;
+    if (C % E || !ew_rows_ok(C / E) || total >= (1L << 31)) return SCD_ERR_ARG;
+    const long rows = total / C;
+    const int scpr = std::min(C / E, 256), sC = scpr * E;
+    const size_t lds = (size_t)4 * sC * sizeof(float);
+    const long nb = ew_resident<bn_bwd_reduce_kernel<T, 1>>(lds);
+    const long rpi = 256 / scpr;
+    const long rpb = std::max<long>(8 * rpi, (rows + nb - 1) / nb + rpi - 1) / rpi * rpi;
+    const int blocks = cdiv(rows, rpb);
+    a.C = sC;
+    a.ld = C;
+    a.rows = (unsigned)rows;
+    a.rows_per_block = (unsigned)rpb;
+    auto next_slice = [sC](auto*& p) { if (p) p += sC; };
+    for (int c0 = 0; c0 < C; c0 += sC) {
+        hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, NL>), dim3(blocks), dim3(256), lds, (hipStream_t)stream, a);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return (int)e;
+        next_slice(a.dout);
+        next_slice(a.mask);
+        if constexpr (NL == 1) { next_slice(a.rsc); next_slice(a.rsh); }
+        for (auto& p : a.y) next_slice(p);
+        for (auto& p : a.mi) next_slice(p);
+        for (auto& p : a.stats) next_slice(p);
+    }
+    return 0;
+}
+
+// the backward apply of total elements in rows of a.C channels (a.nvec is filled in here)
+template <typename T, int NL>
+int launch_bwd_apply(BwdApplyArgs<T, NL> a, long total, void* stream) {
+    constexpr int E = 16 / sizeof(T);
+    if (a.C % E || !ew_rows_ok(a.C / E)) return SCD_ERR_ARG;
+    const long nvec = total / E;
+    const size_t lds = ew_param_lds(bwd_apply_nsrc(NL), a.C, E);
+    if (lds > EW_LDS_MAX) return SCD_ERR_ARG;
+    a.nvec = (unsigned)nvec;
+    const int g = ew_resident<bn_bwd_apply_kernel<T, NL>>(lds);
+    hipLaunchKernelGGL((bn_bwd_apply_kernel<T, NL>), dim3(ew_grid(g, nvec, a.C / E)), dim3(256), lds,
+                       (hipStream_t)stream, a);
+    SCD_RETURN_LAUNCH();
 }
 
 SCD_KERNEL_NS_END
@@ -485,29 +463,8 @@ extern "C" int scd_bn_bwd_reduce(int dtype, const void* dout, const void* mask, 
     SCD_F16_FWD(scd_bn_bwd_reduce, dout, mask, y, relu_scale, relu_shift, mean, invstd, C, total, stats, stream);
     return scd_dispatch_dtype(dtype, [&](auto tag) {
         using T = typename decltype(tag)::type;
-        constexpr int E = 16 / sizeof(T);
-        if (C % E) return SCD_ERR_ARG;
-        const long rows = total / C;
-        const int cpr = C / E;
-        // rows wider than 256 chunks run as channel slices of 256 chunks (ld = the full row)
-        if (!ew_rows_ok(cpr) || total >= (1L << 31)) return SCD_ERR_ARG;
-        const int scpr = std::min(cpr, 256), sC = scpr * E;
-        // one round of resident blocks (at most), at least 8 rows per row lane
-        const long nb = ew_resident<bn_bwd_reduce_kernel<T>>((size_t)4 * sC * sizeof(float));
-        const long rpi = 256 / scpr;
-        const long rpb = std::max<long>(8 * rpi, (rows + nb - 1) / nb + rpi - 1) / rpi * rpi;
-        const int blocks = cdiv(rows, rpb);
-        for (int c0 = 0; c0 < C; c0 += sC) {
-            const T* mk = mask ? (const T*)mask + c0 : nullptr;
-            const float* rs = relu_scale ? relu_scale + c0 : nullptr;
-            const float* rh = relu_shift ? relu_shift + c0 : nullptr;
-            hipLaunchKernelGGL((bn_bwd_reduce_kernel<T>), dim3(blocks), dim3(256), 4 * sC * 4, (hipStream_t)stream,
-                               (const T*)dout + c0, mk, (const T*)y + c0, rs, rh, mean + c0, invstd + c0, sC, C,
-                               (unsigned)rows, (unsigned)rpb, stats + c0);
-            hipError_t e = hipGetLastError();
-            if (e != hipSuccess) return (int)e;
-        }
-        return 0;
+        return launch_bwd_reduce<T, 1>({(const T*)dout, (const T*)mask, {(const T*)y}, relu_scale, relu_shift,
+                                        {mean, invstd}, C, 0, 0, 0, {stats}}, total, stream);
     });
 }
 
@@ -519,26 +476,10 @@ extern "C" int scd_bn_bwd_reduce2(int dtype, const void* dout, const void* mask,
                 stream);
     return scd_dispatch_dtype(dtype, [&](auto tag) {
         using T = typename decltype(tag)::type;
-        constexpr int E = 16 / sizeof(T);
-        if (!dout || !mask || !ya || !yb || C % E) return SCD_ERR_ARG;
-        const long rows = total / C;
-        const int cpr = C / E;
-        if (!ew_rows_ok(cpr) || total >= (1L << 31)) return SCD_ERR_ARG;
-        const int scpr = std::min(cpr, 256), sC = scpr * E;
-        // the same row partition as scd_bn_bwd_reduce (per-thread partial sums identical to two separate passes)
-        const long nb = ew_resident<bn_bwd_reduce_kernel<T>>((size_t)4 * sC * sizeof(float));
-        const long rpi = 256 / scpr;
-        const long rpb = std::max<long>(8 * rpi, (rows + nb - 1) / nb + rpi - 1) / rpi * rpi;
-        const int blocks = cdiv(rows, rpb);
-        for (int c0 = 0; c0 < C; c0 += sC) {
-            hipLaunchKernelGGL((bn_bwd_reduce2_kernel<T>), dim3(blocks), dim3(256), 4 * sC * 4, (hipStream_t)stream,
-                               (const T*)dout + c0, (const T*)mask + c0, (const T*)ya + c0, (const T*)yb + c0,
-                               mean_a + c0, invstd_a + c0, mean_b + c0, invstd_b + c0, sC, C, (unsigned)rows,
-                               (unsigned)rpb, stats_a + c0, stats_b + c0);
-            hipError_t e = hipGetLastError();
-            if (e != hipSuccess) return (int)e;
-        }
-        return 0;
+        if (!dout || !mask || !ya || !yb) return SCD_ERR_ARG;
+        return launch_bwd_reduce<T, 2>({(const T*)dout, (const T*)mask, {(const T*)ya, (const T*)yb},
+                                        {mean_a, invstd_a, mean_b, invstd_b}, C, 0, 0, 0, {stats_a, stats_b}}, total,
+                                       stream);
     });
 }
 
@@ -549,16 +490,9 @@ extern "C" int scd_bn_bwd_apply2(int dtype, const void* dout, const void* mask, 
     return scd_dispatch_dtype(dtype, [&](auto tag) {
         using T = typename decltype(tag)::type;
         constexpr int E = 16 / sizeof(T);
-        if (!dout || !mask || !ya || !yb || !dya || !dyb || C % E || !ew_rows_ok(C / E) || total / E >= (1L << 32))
-            return SCD_ERR_ARG;
-        const long nvec = total / E;
-        const size_t lds = ew_param_lds(6, C, E);
-        if (lds > EW_LDS_MAX) return SCD_ERR_ARG;
-        const int g = ew_resident<bn_bwd_apply2_kernel<T>>(lds);
-        hipLaunchKernelGGL((bn_bwd_apply2_kernel<T>), dim3(ew_grid(g, nvec, C / E)), dim3(256), lds,
-                           (hipStream_t)stream, (const T*)dout, (const T*)mask, (const T*)ya, (const T*)yb, coef_a,
-                           coef_b, C, (unsigned)nvec, (T*)dya, (T*)dyb);
-        SCD_RETURN_LAUNCH();
+        if (!dout || !mask || !ya || !yb || !dya || !dyb || total / E >= (1L << 32)) return SCD_ERR_ARG;
+        return launch_bwd_apply<T, 2>({(const T*)dout, (const T*)mask, {(const T*)ya, (const T*)yb}, {coef_a, coef_b},
+                                       C, 0, {(T*)dya, (T*)dyb}}, total, stream);
     });
 }
 
@@ -568,16 +502,8 @@ extern "C" int scd_bn_bwd_apply(int dtype, const void* dout, const void* mask, c
     SCD_F16_FWD(scd_bn_bwd_apply, dout, mask, y, relu_scale, relu_shift, coef, C, total, dy, dz, stream);
     return scd_dispatch_dtype(dtype, [&](auto tag) {
         using T = typename decltype(tag)::type;
-        constexpr int E = 16 / sizeof(T);
-        if (C % E || !ew_rows_ok(C / E)) return SCD_ERR_ARG;
-        long nvec = total / E;
-        const size_t lds = ew_param_lds(5, C, E);
-        if (lds > EW_LDS_MAX) return SCD_ERR_ARG;
-        const int g = ew_resident<bn_bwd_apply_kernel<T>>(lds);
-        hipLaunchKernelGGL((bn_bwd_apply_kernel<T>), dim3(ew_grid(g, nvec, C / E)), dim3(256), lds,
-                           (hipStream_t)stream, (const T*)dout, (const T*)mask, (const T*)y, relu_scale, relu_shift,
-                           coef, C, (unsigned)nvec, (T*)dy, (T*)dz);
-        SCD_RETURN_LAUNCH();
+        return launch_bwd_apply<T, 1>({(const T*)dout, (const T*)mask, {(const T*)y}, relu_scale, relu_shift, {coef}, C,
+                                       0, {(T*)dy}, (T*)dz}, total, stream);
     });
 }
 
@@ -661,29 +587,29 @@ __device__ __forceinline__ void bn_finalize_channel(int c, double* stats, int nr
     }
 }
 
-__global__ void bn_finalize_kernel(double* stats, int nrep, int C, double count, const float* gamma,
-                                   const float* beta, float* rmean, float* rvar, int64_t* nbt, float momentum,
-                                   float eps, float* mean_o, float* invstd_o, float* scale_o, float* shift_o) {
-    const int c = blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
-    if (c >= C) return;
-    bn_finalize_channel(c, stats, nrep, C, count, gamma, beta, rmean, rvar, momentum, eps, mean_o, invstd_o, scale_o,
-                        shift_o, nbt);
-}
-
-// up to SCD_BN_FIN_MAX layers in one launch (scd_bn_finalize_n): layer i owns blocks [b0[i], b0[i + 1])
+// 1 .. SCD_BN_FIN_MAX layers in one launch (forward or backward finalize): layer i owns blocks [b0[i], b0[i + 1])
+template <typename Args>
 struct FinN {
-    scd_bn_fin_args l[SCD_BN_FIN_MAX];
+    Args l[SCD_BN_FIN_MAX];
     int b0[SCD_BN_FIN_MAX + 1];
     int n;
 };
-__global__ void bn_finalize_n_kernel(FinN f) {
+// this block's layer, and this wave's channel c in it (one wave per channel, 4 per 256-thread block)
+template <typename Args>
+__device__ __forceinline__ const Args& fin_layer(const FinN<Args>& f, int& c) {
     int i = 0;
 #pragma unroll
     for (int k = 1; k < SCD_BN_FIN_MAX; ++k)
         if (k < f.n && (int)blockIdx.x >= f.b0[k]) i = k;
-    const scd_bn_fin_args& a = f.l[i];
-    const int blk = blockIdx.x - f.b0[i];
-    const int c = blk * (blockDim.x / 64) + (threadIdx.x >> 6);
+    const Args& a = f.l[i];
+    c = (blockIdx.x - f.b0[i]) * (blockDim.x / 64) + (threadIdx.x >> 6);
+    return a;
+}
+inline int fin_blocks(int C) { return (C + 3) / 4; }
+
+__global__ void bn_finalize_n_kernel(FinN<scd_bn_fin_args> f) {
+    int c;
+    const scd_bn_fin_args& a = fin_layer(f, c);
     if (c >= a.C) return;
     bn_finalize_channel(c, a.stats, a.nrep, a.C, a.count, a.gamma, a.beta, a.running_mean, a.running_var, a.momentum,
                         a.eps, a.mean, a.invstd, a.scale, a.shift, a.num_batches);
@@ -708,6 +634,7 @@ __device__ __forceinline__ void bn_bwd_finalize_channel(int c, double* stats, in
     coef[2 * C + c] = -sc * k1 + sc * is * k2 * mean[c];
 }
 
+// (kept beside the _n kernel: through the layer array a single layer's launch took 0.3 us longer at C = 2048)
 __global__ void bn_bwd_finalize_kernel(double* stats, int nrep, int C, double count, const float* gamma,
                                        const float* mean, const float* invstd, float* dgamma, float* dbeta,
                                        float gscale, float* coef) {
@@ -716,24 +643,32 @@ __global__ void bn_bwd_finalize_kernel(double* stats, int nrep, int C, double co
     bn_bwd_finalize_channel(c, stats, nrep, C, count, gamma, mean, invstd, dgamma, dbeta, gscale, coef);
 }
 
-struct BwdFinN {
-    scd_bn_bwd_fin_args l[SCD_BN_FIN_MAX];
-    int b0[SCD_BN_FIN_MAX + 1];
-    int n;
-};
-__global__ void bn_bwd_finalize_n_kernel(BwdFinN f) {
-    int i = 0;
-#pragma unroll
-    for (int k = 1; k < SCD_BN_FIN_MAX; ++k)
-        if (k < f.n && (int)blockIdx.x >= f.b0[k]) i = k;
-    const scd_bn_bwd_fin_args& a = f.l[i];
-    const int c = (blockIdx.x - f.b0[i]) * (blockDim.x / 64) + (threadIdx.x >> 6);
+__global__ void bn_bwd_finalize_n_kernel(FinN<scd_bn_bwd_fin_args> f) {
+    int c;
+    const scd_bn_bwd_fin_args& a = fin_layer(f, c);
     if (c >= a.C) return;
     bn_bwd_finalize_channel(c, a.stats, a.nrep, a.C, a.count, a.gamma, a.mean, a.invstd, a.dgamma, a.dbeta, a.gscale,
                             a.coef);
 }
 
-inline int fin_blocks(int C) { return (C + 3) / 4; }   // 4 waves (channels) per 256-thread block
+// the launch of Kernel over layers[0 .. n), each of which passes the entry point's own test `ok`
+template <auto Kernel, typename Args, typename Ok>
+int launch_finalize_n(const Args* layers, int n, Ok ok, void* stream) {
+    if (!layers || n < 1 || n > SCD_BN_FIN_MAX) return SCD_ERR_ARG;
+    FinN<Args> f;
+    memset(&f, 0, sizeof(f));
+    f.n = n;
+    int blocks = 0;
+    for (int i = 0; i < n; ++i) {
+        if (!ok(layers[i])) return SCD_ERR_ARG;
+        f.l[i] = layers[i];
+        f.b0[i] = blocks;
+        blocks += fin_blocks(layers[i].C);
+    }
+    f.b0[n] = blocks;
+    hipLaunchKernelGGL(Kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, f);
+    SCD_RETURN_LAUNCH();
+}
 
 }  // namespace
 
@@ -755,45 +690,20 @@ extern "C" int scd_bn_finalize(double* stats, int nrep, int C, double count, con
                                const float* beta, float* running_mean, float* running_var, int64_t* num_batches,
                                float momentum, float eps, float* mean, float* invstd, float* scale, float* shift,
                                void* stream) {
-    hipLaunchKernelGGL(bn_finalize_kernel, dim3(fin_blocks(C)), dim3(256), 0, (hipStream_t)stream, stats, nrep, C,
-                       count, gamma, beta, running_mean, running_var, num_batches, momentum, eps, mean, invstd, scale,
-                       shift);
-    SCD_RETURN_LAUNCH();
+    const scd_bn_fin_args layer = {stats, nrep, C, count, gamma, beta, running_mean, running_var, num_batches,
+                                   momentum, eps, mean, invstd, scale, shift};
+    return scd_bn_finalize_n(&layer, 1, stream);
 }
 
 extern "C" int scd_bn_finalize_n(const scd_bn_fin_args* layers, int n, void* stream) {
-    if (!layers || n < 1 || n > SCD_BN_FIN_MAX) return SCD_ERR_ARG;
-    FinN f;
-    memset(&f, 0, sizeof(f));
-    f.n = n;
-    int blocks = 0;
-    for (int i = 0; i < n; ++i) {
-        if (layers[i].C <= 0) return SCD_ERR_ARG;
-        f.l[i] = layers[i];
-        f.b0[i] = blocks;
-        blocks += fin_blocks(layers[i].C);
-    }
-    f.b0[n] = blocks;
-    hipLaunchKernelGGL(bn_finalize_n_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, f);
-    SCD_RETURN_LAUNCH();
+    return launch_finalize_n<bn_finalize_n_kernel>(layers, n, [](const scd_bn_fin_args& l) { return l.C > 0; },
+                                                   stream);
 }
 
 extern "C" int scd_bn_bwd_finalize_n(const scd_bn_bwd_fin_args* layers, int n, void* stream) {
-    if (!layers || n < 1 || n > SCD_BN_FIN_MAX) return SCD_ERR_ARG;
-    BwdFinN f;
-    memset(&f, 0, sizeof(f));
-    f.n = n;
-    int blocks = 0;
-    for (int i = 0; i < n; ++i) {
-        if (layers[i].C <= 0 || !layers[i].stats || !layers[i].invstd || !layers[i].mean || !layers[i].coef)
-            return SCD_ERR_ARG;
-        f.l[i] = layers[i];
-        f.b0[i] = blocks;
-        blocks += fin_blocks(layers[i].C);
-    }
-    f.b0[n] = blocks;
-    hipLaunchKernelGGL(bn_bwd_finalize_n_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, f);
-    SCD_RETURN_LAUNCH();
+    return launch_finalize_n<bn_bwd_finalize_n_kernel>(
+        layers, n,
+        [](const scd_bn_bwd_fin_args& l) { return l.C > 0 && l.stats && l.invstd && l.mean && l.coef; }, stream);
 }
 
 extern "C" int scd_bn_bwd_finalize(double* stats, int nrep, int C, double count, const float* gamma,

@@ -1265,20 +1265,23 @@ def bn_finalize(bn, stats, C, count, training=True):
     st = _bn_state(C, bn.weight.device)
     if training:
         return _bn_finalize_launch(bn, st, stats, _allreduce_stats(stats, C), C, count)
-    else:
-        L.call("scd_bn_finalize", 0, 0, C, 1.0, ptr(bn.weight), ptr(bn.bias), ptr(bn.running_mean),
-               ptr(bn.running_var), 0, 0.0, float(bn.eps), ptr(st.mean), ptr(st.invstd), ptr(st.scale),
-               ptr(st.shift), stream())
     st.count = count
+    L.call("scd_bn_finalize", *_bn_fin_args(bn, st, None, 0, C), stream())
     return st
 
 
+def _bn_fin_args(bn, st, stats, nrep, C):
+    """A layer's finalize arguments in the order of scd_bn_finalize and of struct scd_bn_fin_args (st.count set).
+    stats None: eval mode -- the running statistics are read, nothing of the module is updated."""
+    ev = stats is None
+    return (ptr(stats), nrep, C, 1.0 if ev else float(st.count), ptr(bn.weight), ptr(bn.bias), ptr(bn.running_mean),
+            ptr(bn.running_var), 0 if ev else ptr(bn.num_batches_tracked), 0.0 if ev else float(bn.momentum),
+            float(bn.eps), ptr(st.mean), ptr(st.invstd), ptr(st.scale), ptr(st.shift))
+
+
 def _bn_finalize_launch(bn, st, stats, nrep, C, count):
-    count = count * bn_sync_world()
-    L.call("scd_bn_finalize", ptr(stats), nrep, C, float(count), ptr(bn.weight), ptr(bn.bias),
-           ptr(bn.running_mean), ptr(bn.running_var), ptr(bn.num_batches_tracked), float(bn.momentum),
-           float(bn.eps), ptr(st.mean), ptr(st.invstd), ptr(st.scale), ptr(st.shift), stream())
-    st.count = count
+    st.count = count * bn_sync_world()
+    L.call("scd_bn_finalize", *_bn_fin_args(bn, st, stats, nrep, C), stream())
     return st
 
 
@@ -1298,9 +1301,7 @@ def bn_finalize_pair(bn_a, stats_a, Ca, count_a, bn_b, stats_b, Cb, count_b):
     for i, (bn, stats, C, count) in enumerate(((bn_a, sa, Ca, count_a), (bn_b, sb, Cb, count_b))):
         st = _bn_state(C, bn.weight.device)
         st.count = count * bn_sync_world()
-        args[i] = L.BnFinArgs(ptr(stats), nrep, C, float(st.count), ptr(bn.weight), ptr(bn.bias), ptr(bn.running_mean),
-                              ptr(bn.running_var), ptr(bn.num_batches_tracked), float(bn.momentum), float(bn.eps),
-                              ptr(st.mean), ptr(st.invstd), ptr(st.scale), ptr(st.shift))
+        args[i] = L.BnFinArgs(*_bn_fin_args(bn, st, stats, nrep, C))
         sts.append(st)
     L.call("scd_bn_finalize_n", args, 2, stream())
     return sts[0], sts[1]
@@ -1368,8 +1369,7 @@ def bn_backward_pair(bn_a, st_a, y_a, bn_b, st_b, y_b, dout, mask):
     ca, cb = torch.empty(2, 3 * C, device=sa.device).unbind(0)
     args = (L.BnBwdFinArgs * 2)()
     for i, (bn, st, stats, coef) in enumerate(((bn_a, st_a, sa, ca), (bn_b, st_b, sb, cb))):
-        args[i] = L.BnBwdFinArgs(ptr(stats), nrep, C, float(st.count), ptr(bn.weight), ptr(st.mean), ptr(st.invstd),
-                                 ptr(grad_of(bn.weight)), ptr(grad_of(bn.bias)), alpha / bn_sync_world(), ptr(coef))
+        args[i] = L.BnBwdFinArgs(*_bn_bwd_fin_args(bn, st, stats, nrep, C, alpha, coef))
     L.call("scd_bn_bwd_finalize_n", args, 2, stream())
     dya, dyb = torch.empty_like(y_a), torch.empty_like(y_b)
     t0 = ClassTimer.begin()
@@ -1386,11 +1386,15 @@ def bn_backward_coef(bn, st, stats, C, alpha=1.0):
     return _bn_bwd_finalize_launch(bn, st, stats, _allreduce_stats(stats, C), C, alpha)
 
 
+def _bn_bwd_fin_args(bn, st, stats, nrep, C, alpha, coef):
+    """A layer's backward finalize arguments in the order of scd_bn_bwd_finalize and of struct scd_bn_bwd_fin_args."""
+    return (ptr(stats), nrep, C, float(st.count), ptr(bn.weight), ptr(st.mean), ptr(st.invstd),
+            ptr(grad_of(bn.weight)), ptr(grad_of(bn.bias)), alpha / bn_sync_world(), ptr(coef))
+
+
 def _bn_bwd_finalize_launch(bn, st, stats, nrep, C, alpha):
     coef = torch.empty(3 * C, device=stats.device)
-    L.call("scd_bn_bwd_finalize", ptr(stats), nrep, C, float(st.count), ptr(bn.weight), ptr(st.mean),
-           ptr(st.invstd), ptr(grad_of(bn.weight)), ptr(grad_of(bn.bias)), alpha / bn_sync_world(), ptr(coef),
-           stream())
+    L.call("scd_bn_bwd_finalize", *_bn_bwd_fin_args(bn, st, stats, nrep, C, alpha, coef), stream())
     return coef
 
 

@@ -714,26 +714,37 @@ def test_bn_bwd_apply_long_runs_unrolled_loop(dtype, kind):
     check_bwd_apply(_ops(), dtype, 64, long_rows(64, dtype), 9, (kind,), (True,))
 
 
+def check_bwd_apply2(ops, dtype, C, rows):
+    g = gen(41 * C + rows)
+    dout = normal(g, (rows, C), dtype)
+    ya = normal(g, (rows, C), dtype)
+    yb = normal(g, (rows, C), dtype, mean=-0.5, std=2.0)
+    mask = normal(g, (rows, C), dtype)
+    ca, cb = random_coef(g, C), random_coef(g, C) * 0.75
+    dz64, _ = masked(dout, ya, 1, mask, None, None)
+    dya, dyb = torch.full_like(ya, float("nan")), torch.full_like(ya, float("nan"))
+    ops.L.call("scd_bn_bwd_apply2", ops.dt(ya), ops.ptr(dout), ops.ptr(mask), ops.ptr(ya), ops.ptr(yb), ops.ptr(ca),
+               ops.ptr(cb), C, ya.numel(), ops.ptr(dya), ops.ptr(dyb), ops.stream())
+    torch.cuda.synchronize()
+    for got, yv, coef, name in ((dya, ya, ca, "a"), (dyb, yb, cb, "b")):
+        ref, mag = bwd_apply_ref(dz64, yv, coef)
+        assert_elementwise(got, ref, ULP_OUT[dtype] * ref.abs() + 4 * U24 * mag,
+                           "bwd_apply2 %s %s C %d rows %d" % (name, dtype, C, rows))
+
+
 @pytest.mark.parametrize("dtype,C", DC, ids=DC_IDS)
 def test_bn_bwd_apply2_matches_float64(dtype, C):
     """Both layers of the pair kernel: dy_a = a_a dz + b_a y_a + c_a, dy_b likewise, dz masked by the stored activation."""
     ops = _ops()
     for rows in ragged_rows(C, dtype):
-        g = gen(41 * C + rows)
-        dout = normal(g, (rows, C), dtype)
-        ya = normal(g, (rows, C), dtype)
-        yb = normal(g, (rows, C), dtype, mean=-0.5, std=2.0)
-        mask = normal(g, (rows, C), dtype)
-        ca, cb = random_coef(g, C), random_coef(g, C) * 0.75
-        dz64, _ = masked(dout, ya, 1, mask, None, None)
-        dya, dyb = torch.full_like(ya, float("nan")), torch.full_like(ya, float("nan"))
-        ops.L.call("scd_bn_bwd_apply2", ops.dt(ya), ops.ptr(dout), ops.ptr(mask), ops.ptr(ya), ops.ptr(yb), ops.ptr(ca),
-                   ops.ptr(cb), C, ya.numel(), ops.ptr(dya), ops.ptr(dyb), ops.stream())
-        torch.cuda.synchronize()
-        for got, yv, coef, name in ((dya, ya, ca, "a"), (dyb, yb, cb, "b")):
-            ref, mag = bwd_apply_ref(dz64, yv, coef)
-            assert_elementwise(got, ref, ULP_OUT[dtype] * ref.abs() + 4 * U24 * mag,
-                               "bwd_apply2 %s %s C %d rows %d" % (name, dtype, C, rows))
+        check_bwd_apply2(ops, dtype, C, rows)
+
+
+@pytest.mark.parametrize("dtype", [F32, BF16], ids=["float32", "bfloat16"])
+def test_bn_bwd_apply2_long_runs(dtype):
+    """More than four grid strides of vectors and an odd row count: the pair kernel's main loop over several strides
+    and a ragged last one."""
+    check_bwd_apply2(_ops(), dtype, 64, long_rows(64, dtype))
 
 
 # ------------------------------------------------------------------ 6. one composite against autograd

@@ -114,8 +114,10 @@ def _loop_span(lines):
 # test turns into them silently
 BRANCH_CEILING = {
     ("stem.hip", r"stem_bwd_fused_kernel"): 4,
-    ("bn.hip", r"bn_bwd_apply_kernelIDF16bE"): 4,
-    ("bn.hip", r"bn_bwd_reduce_kernelIDF16bE"): 4,
+    ("bn.hip", r"bn_bwd_apply_kernelIDF16bLi1E"): 4,
+    ("bn.hip", r"bn_bwd_apply_kernelIDF16bLi2E"): 4,
+    ("bn.hip", r"bn_bwd_reduce_kernelIDF16bLi1E"): 4,
+    ("bn.hip", r"bn_bwd_reduce_kernelIDF16bLi2E"): 4,
 }
 
 

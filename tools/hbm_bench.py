@@ -86,7 +86,18 @@ def main():
         report("bn_bwd_apply mask+dz " + tag, timed(lambda: L.call(
             "scd_bn_bwd_apply", L.DT_BF16, d.data_ptr(), r.data_ptr(), y.data_ptr(), 0, 0,
             coef.data_ptr(), C, n, out.data_ptr(), r.data_ptr(), st()), a.reps), 5 * B)
-        del y, r, d, out
+        # the pair kernels of a residual join: dout, mask and two layers' y (-> two layers' dy)
+        yb, outb = torch.randn(N, H, W, C, device=dev).to(bf), torch.empty_like(y)
+        mask = torch.randn(N, H, W, C, device=dev).to(bf)
+        stats_b = torch.zeros_like(stats)
+        report("bn_bwd_reduce2 " + tag, timed(lambda: L.call(
+            "scd_bn_bwd_reduce2", L.DT_BF16, d.data_ptr(), mask.data_ptr(), y.data_ptr(), yb.data_ptr(),
+            mean.data_ptr(), invstd.data_ptr(), mean.data_ptr(), invstd.data_ptr(), C, n, stats.data_ptr(),
+            stats_b.data_ptr(), st()), a.reps), 4 * B)
+        report("bn_bwd_apply2 " + tag, timed(lambda: L.call(
+            "scd_bn_bwd_apply2", L.DT_BF16, d.data_ptr(), mask.data_ptr(), y.data_ptr(), yb.data_ptr(),
+            coef.data_ptr(), coef.data_ptr(), C, n, out.data_ptr(), outb.data_ptr(), st()), a.reps), 6 * B)
+        del y, r, d, out, yb, outb, mask
 
     if "heads" in groups:
         heads_rows(a, report, dev, bf, st)
