@@ -352,6 +352,27 @@ int scd_centernet_loss_fwd(const float* heat, const float* gt, long n_heat, cons
 int scd_centernet_loss_bwd_scale(float* g_heat, long n_heat, int N, int HW, const int64_t* inds, int K, float* g_regr,
                                  int Cr, float* g_off, int Co, const float* factors, const float* go, void* stream);
 
+/* CornerNet's associative-embedding loss (models/losses/embeddings.py embeddingLoss with a uint8 mask)
+ * behind the focal terms of scd_focal_fwd.  tl_tag / br_tag (N,1,HW) fp32 maps, tl_inds / br_inds (N,K) int64 cells,
+ * valid (N,K) u8, K <= 64.  Per image with n valid slots, e = the tags at the slots' cells, m = (e_tl + e_br) / 2:
+ *   pull = sum_k [(e_tl-m)^2 + (e_br-m)^2] / (n + 1e-4),
+ *   push = sum_{i,j} [relu(1 - |m_i-m_j|) - 1/(n + 1e-4)] / (n(n-1) + 1e-4)   (diagonal included; n = 0 adds nothing),
+ * in float64 from the float32 tags, the normalisers rounded to float32 as the reference's are.
+ * scd_corner_ae_fwd (two launches): one workgroup per image writes its pull / push to ae_acc[2b], ae_acc[2b+1]
+ * (N*2 doubles, any contents on entry) and the per-slot tag gradients, times w_pull / w_push, to gs_tl / gs_br (N,K);
+ * then the finalize: out = [loss, focal x nfocal, w_pull*pull, w_push*push] (3 + nfocal floats), factors (nfocal) =
+ * the focal backward scales, focal_acc (nfocal * 64 * 4 doubles, filled by nfocal scd_focal_fwd calls) re-zeroed.
+ * scd_corner_ae_bwd (one launch) writes the two gradient maps g_tl / g_br (N,1,HW) whole: at each pixel the sum, in
+ * slot order, of the gradients of the valid slots naming it, times go[0] (go NULL: 1); zero elsewhere.
+ * SCD_ERR_ARG and no launch for a NULL pointer (but go), N < 1, HW < 1, N*HW >= 2^31, K < 1 or K > 64. */
+int scd_corner_ae_fwd(const float* tl_tag, const float* br_tag, int N, int HW, const int64_t* tl_inds,
+                      const int64_t* br_inds, const uint8_t* valid, int K, float w_pull, float w_push,
+                      double* focal_acc, int nfocal, double* ae_acc, float* gs_tl, float* gs_br, float* out,
+                      float* factors, void* stream);
+int scd_corner_ae_bwd(const float* gs_tl, const float* gs_br, int N, int HW, const int64_t* tl_inds,
+                      const int64_t* br_inds, const uint8_t* valid, int K, const float* go, float* g_tl, float* g_br,
+                      void* stream);
+
 /* Keep map for scd_conv_gemm_heads_keep from the loss targets' gather indices inds (N,K) int64 (the `inds` target of
  * CenterNetLoss, centerNetOffset.py:199-214): keep[n*HW + inds[n][k]] = 1 for every slot, after clearing the pixels
  * the previous call set (prev: nprev >= N*K int64, -1-filled on first use, updated in place; keep zero-filled on
@@ -389,6 +410,13 @@ int scd_render_corner_targets(const float* locs, const int* counts, int B, int K
 int scd_render_corner_targets_split(const float* locs, const int* counts, int B, int K, int H, float threshold,
                                     float* heat, float* tl, float* br, uint8_t* mask, float* regr, int64_t* inds,
                                     int split, void* stream);
+/* The cells CornerNet's embedding loss gathers its tags at, from the rows scd_render_corner_targets renders (the same
+ * device functions decode the centre's cell and the two corners): tl_inds / br_inds (B,K) int64 = y*size + x of the
+ * slot's top-left / bottom-right cell, valid (B,K) u8 = 1 exactly where that renderer draws both corners of slot k
+ * (k < min(counts[b], K), the centre on the map, both corners finite); an invalid slot has both indices 0.
+ * SCD_ERR_ARG and no launch for a NULL pointer, B < 1, K < 1, K > 64, size < 1 or size*size >= 2^31. */
+int scd_corner_tag_inds(const float* locs, const int* counts, int B, int K, int size, int64_t* tl_inds,
+                        int64_t* br_inds, uint8_t* valid, void* stream);
 /* SCD tile augmentation (datasets/scds/scdx16p100.py:416-441, datasets/argumentations.py:38-64):
  * out[b] = (flip(in[b]) - mean) / sqrt(var) * jitter[b] + noise * noise_sv, mean/var over the flipped tile (fp64
  * sums).  flips (B,2) u8 device [x (dim 2), y (dim 1)], nullable; jitter (B) device factors (1 + 0.05 g), nullable;
@@ -491,6 +519,17 @@ size_t scd_decode_workspace(int N, int HW);
 int scd_decode_topk(const float* heat, int N, int H, int W, int K, const float* offset, int od_off,
                     const float* regr, int od_regr, float* scores, int64_t* inds, int64_t* ys, int64_t* xs,
                     float* off_out, float* regr_out, void* workspace, void* stream);
+/* decodeCornerNet's corner pairing (cornerNetLegacy.py:332-446) for one category, one launch, one workgroup per image:
+ * top-K corners of the two maps (scores, inds, ys, xs (N,K) as scd_decode_topk writes them; scores >= 0) and the tag
+ * maps tl_tag / br_tag (N,1,HW), gathered at inds.  Pair (i, j): score = (s_tl[i] + s_br[j]) / 2, dropped when
+ * |tag_tl[i] - tag_br[j]| > threshold, x_br < x_tl or y_br < y_tl.  det (N,D,8) fp32: the first nvalid[b] =
+ * min(#surviving, D) rows are [x_tl, y_tl, x_br, y_br, score, s_tl, s_br, 0] ordered by score descending, then flat
+ * index i*K + j ascending; the other rows are [0, 0, 0, 0, -1, 0, 0, 0].  The K*K candidates are never stored.
+ * SCD_ERR_ARG and no launch for a NULL pointer, N < 1, K < 1, K > 128, HW < 1, D < 1, D > 1024 or D > K*K. */
+int scd_corner_pairs(const float* tl_scores, const int64_t* tl_inds, const int64_t* tl_ys, const int64_t* tl_xs,
+                     const float* br_scores, const int64_t* br_inds, const int64_t* br_ys, const int64_t* br_xs,
+                     const float* tl_tag, const float* br_tag, int N, int K, int HW, float threshold, int D, float* det,
+                     int* nvalid, void* stream);
 
 /* ---- validation metrics (models/centerNetOffset.py:253-354, evaluations/detection.py:11-230,
  * trainer/model/centerOffsetRes10.py:18-106) ----

@@ -2,7 +2,7 @@
 
 Same default keys and the same overlay rule: a JSON config replaces only keys that already
 exist (configuration.py:150-153); string values may reference other keys as `{key}` format
-fields.  Five keys are added: ``computeDtype`` ("bf16" | "fp16" | "fp32"), the MFMA precision of the
+fields.  Six keys are added: ``computeDtype`` ("bf16" | "fp16" | "fp32"), the MFMA precision of the
 HIP path (the reference trains in fp32 without AMP), ``stepGraph`` (true | false, default false):
 replay the training step as a captured HIP graph after two eager steps (single-process runs;
 scdhip/graph.py -- measured slower than eager issue on ROCm 7), ``rotateAugmentation``
@@ -12,7 +12,10 @@ drawn uniformly from [-value, value] (the reference holds this s
 labels) to the device at the first training batch and build every batch there from the host's random draws
 (it raises when the archive does not fit into the device's free memory), and ``cornerTargets``
 (true | false, default false): the `.d` dataset plugins serve CornerNet's target layout [heat, mask, regr, tl, br],
-training batches and validation set alike, the corner maps rendered by scd_render_corner_targets.
+training batches and validation set alike, the corner maps rendered by scd_render_corner_targets, and
+``cornerEmbeddings`` (true | false, default false; needs cornerTargets): the corner layout grows to [heat, mask, regr,
+tl, br, tl_inds, br_inds, valid], the cells and slots cornerNetAE's embedding loss gathers its tags at
+(scd_corner_tag_inds); `syntheticCorner` reads it too.
 """
 import os
 
@@ -53,6 +56,7 @@ class Configuration:
         c["rotateAugmentation"] = 0.0
         c["residentDataset"] = False
         c["cornerTargets"] = False
+        c["cornerEmbeddings"] = False
         self.config = c
 
     # -- formatted / plain accessors (configuration.py:46-146)
@@ -94,6 +98,7 @@ class Configuration:
     rotateAugmentation = property(lambda s: float(s.config["rotateAugmentation"]))
     residentDataset = property(lambda s: bool(s.config["residentDataset"]))
     cornerTargets = property(lambda s: bool(s.config["cornerTargets"]))
+    cornerEmbeddings = property(lambda s: bool(s.config["cornerEmbeddings"]))
 
     def useGPU(self):
         # a bound method, hence always truthy when tested without a call (reference quirk)

@@ -82,6 +82,19 @@ struct LossFin {
     float l1w[8];
 };
 
+// focal term f from its accumulator replicas (focal.py:47-51: no positives -> -negL ; else -(posL+negL)/#pos) and
+// the factor its saved gradient is scaled by in backward
+__device__ __forceinline__ float focal_finalize(const double* facc, int f, float* factor) {
+    double pl = 0, nl = 0, np = 0;
+    for (int r = 0; r < SCD_STAT_REPLICAS; ++r) {
+        const double* a = facc + ((long)f * SCD_STAT_REPLICAS + r) * FOCAL_ACC;
+        pl += a[0]; nl += a[1]; np += a[2];
+    }
+    const float posl = (float)pl, negl = (float)nl, npos = (float)np;
+    *factor = np == 0.0 ? -1.f : -1.f / npos;
+    return np == 0.0 ? -negl : -(posl + negl) / npos;
+}
+
 // one block of 64 threads: thread 0 forms the loss terms, then the block re-zeroes both accumulators
 // (persistent, consumer-cleared buffers: no memset launch before the next step's loss)
 __global__ void loss_finalize_kernel(double* facc, int nfocal, double* lacc, int nl1, LossFin w, float* out,
@@ -90,16 +103,8 @@ __global__ void loss_finalize_kernel(double* facc, int nfocal, double* lacc, int
     if (threadIdx.x == 0) {
         double total = 0.0;
         for (int f = 0; f < nfocal; ++f) {
-            double pl = 0, nl = 0, np = 0;
-            for (int r = 0; r < SCD_STAT_REPLICAS; ++r) {
-                const double* a = facc + ((long)f * SCD_STAT_REPLICAS + r) * FOCAL_ACC;
-                pl += a[0]; nl += a[1]; np += a[2];
-            }
-            // focal.py:47-51: no positives -> -negL ; else -(posL+negL)/#pos
-            const float posl = (float)pl, negl = (float)nl, npos = (float)np;
-            const float v = np == 0.0 ? -negl : -(posl + negl) / npos;
+            const float v = focal_finalize(facc, f, factors + f);
             out[1 + f] = v;
-            factors[f] = np == 0.0 ? -1.f : -1.f / npos;
             total += v;
         }
         for (int l = 0; l < nl1; ++l) {
@@ -279,26 +284,23 @@ __global__ void decode_nms_kernel(const float* heat, int N, int H, int W, int k,
     }
 }
 
-// one 1024-thread block per image: radix-select the K-th largest (non-negative floats
-// order like their bit patterns), collect, then bitonic sort by (score desc, index asc).
-__global__ __launch_bounds__(1024) void decode_select_kernel(const float* t, int HW, int W, int K,
-                                                             const float* offset, int od_off, const float* regr,
-                                                             int od_regr, float* scores, int64_t* inds, int64_t* ys,
-                                                             int64_t* xs, float* off_out, float* regr_out) {
+// The K largest of n candidates, sorted, for one workgroup: cand(i, bits) says whether candidate i takes part and
+// gives its score's bit pattern (non-negative floats order like their bit patterns).  Radix-select the K-th largest
+// (four 8-bit passes), collect, then bitonic sort by (score desc, index asc).  At least K candidates must take part,
+// K <= 1024; on return keys[0..K) hold (bits << 32) | (0xFFFFFFFF - index), every thread past a barrier.
+template <typename Cand>
+__device__ __forceinline__ void select_sorted_keys(Cand cand, int n, int K, unsigned long long* keys) {
     __shared__ unsigned hist[256];
     __shared__ unsigned s_prefix, s_krem, s_count, s_eqtaken;
-    __shared__ unsigned long long keys[1024];
-    const int n = blockIdx.x;
-    const unsigned* bits = (const unsigned*)(t + (long)n * HW);
     const int tid = threadIdx.x;
     unsigned prefix = 0, pmask = 0, krem = (unsigned)K;
     for (int pass = 0; pass < 4; ++pass) {
         const int shift = 24 - 8 * pass;
         for (int i = tid; i < 256; i += blockDim.x) hist[i] = 0;
         __syncthreads();
-        for (int i = tid; i < HW; i += blockDim.x) {
-            const unsigned b = bits[i];
-            if ((b & pmask) == prefix) atomicAdd(&hist[(b >> shift) & 255], 1u);
+        for (int i = tid; i < n; i += blockDim.x) {
+            unsigned b;
+            if (cand(i, b) && (b & pmask) == prefix) atomicAdd(&hist[(b >> shift) & 255], 1u);
         }
         __syncthreads();
         if (tid == 0) {
@@ -321,21 +323,22 @@ __global__ __launch_bounds__(1024) void decode_select_kernel(const float* t, int
     for (int i = tid; i < 1024; i += blockDim.x) keys[i] = 0ull;
     __syncthreads();
     const unsigned thr = prefix;
-    for (int i = tid; i < HW; i += blockDim.x) {
-        const unsigned b = bits[i];
-        if (b > thr) {
+    for (int i = tid; i < n; i += blockDim.x) {
+        unsigned b;
+        if (cand(i, b) && b > thr) {
             const unsigned slot = atomicAdd(&s_count, 1u);
             keys[slot] = ((unsigned long long)b << 32) | (unsigned)(0xFFFFFFFFu - (unsigned)i);
         }
     }
     __syncthreads();
     // ties at the threshold: take the lowest indices, in index order (chunks of blockDim)
-    for (int base = 0; base < HW; base += blockDim.x) {
+    for (int base = 0; base < n; base += blockDim.x) {
         __syncthreads();
         const unsigned taken = s_eqtaken;
         if (taken >= krem) break;
         const int i = base + tid;
-        const bool eq = i < HW && bits[i] == thr;
+        unsigned b = 0;
+        const bool eq = i < n && cand(i, b) && b == thr;
         // block-wide exclusive prefix count of eq flags
         const unsigned long long bal = __ballot(eq);
         const int lane = tid & 63, wv = tid >> 6;
@@ -373,6 +376,19 @@ __global__ __launch_bounds__(1024) void decode_select_kernel(const float* t, int
             __syncthreads();
         }
     }
+}
+
+// one 1024-thread block per image: the K largest NMS'd scores (select_sorted_keys over the map's pixels) and the
+// gathers at them
+__global__ __launch_bounds__(1024) void decode_select_kernel(const float* t, int HW, int W, int K,
+                                                             const float* offset, int od_off, const float* regr,
+                                                             int od_regr, float* scores, int64_t* inds, int64_t* ys,
+                                                             int64_t* xs, float* off_out, float* regr_out) {
+    __shared__ unsigned long long keys[1024];
+    const int n = blockIdx.x;
+    const unsigned* bits = (const unsigned*)(t + (long)n * HW);
+    const int tid = threadIdx.x;
+    select_sorted_keys([bits](int i, unsigned& b) { b = bits[i]; return true; }, HW, K, keys);
     for (int k = tid; k < K; k += blockDim.x) {
         const unsigned long long key = keys[k];
         const unsigned b = (unsigned)(key >> 32);
@@ -385,6 +401,200 @@ __global__ __launch_bounds__(1024) void decode_select_kernel(const float* t, int
         for (int c = 0; c < od_off; ++c) off_out[o * od_off + c] = offset[((long)n * od_off + c) * HW + idx];
         if (regr)
             for (int c = 0; c < od_regr; ++c) regr_out[o * od_regr + c] = regr[((long)n * od_regr + c) * HW + idx];
+    }
+}
+
+// ---------------------------------------------------------------- CornerNet: corner pairing
+// decodeCornerNet's K x K pairing (cornerNetLegacy.py:332-446) for one category, one workgroup per image: the
+// candidates (i, j) -- top-left corner i with bottom-right corner j -- are formed on the fly from the K-length arrays
+// in LDS, never stored.  score = (s_tl[i] + s_br[j]) / 2; a pair is dropped when |tag_tl[i] - tag_br[j]| > threshold,
+// x_br < x_tl or y_br < y_tl.  The D best survivors by (score desc, flat index i*K + j asc) become rows
+// [x_tl, y_tl, x_br, y_br, score, s_tl, s_br, 0]; the rest of the D rows have score -1 and zeros.  Scores must be
+// non-negative (they are sigmoids); a corner whose index lies outside the map pairs with nothing.
+constexpr int PAIR_MAXK = 128;
+
+__global__ __launch_bounds__(1024) void corner_pairs_kernel(const float* s_tl, const int64_t* i_tl, const int64_t* y_tl,
+                                                            const int64_t* x_tl, const float* s_br, const int64_t* i_br,
+                                                            const int64_t* y_br, const int64_t* x_br, const float* tag_tl,
+                                                            const float* tag_br, int K, int HW, float threshold, int D,
+                                                            float* det, int* nvalid) {
+    __shared__ unsigned long long keys[1024];
+    __shared__ float sc[2][PAIR_MAXK], tg[2][PAIR_MAXK];
+    __shared__ int cx[2][PAIR_MAXK], cy[2][PAIR_MAXK], ok[2][PAIR_MAXK];
+    __shared__ unsigned s_nvalid;
+    const int n = blockIdx.x, tid = threadIdx.x;
+    for (int k = tid; k < 2 * K; k += blockDim.x) {
+        const int c = k >= K, kk = k - c * K;
+        const long o = (long)n * K + kk;
+        const int64_t ind = (c ? i_br : i_tl)[o];
+        const bool in = ind >= 0 && ind < HW;
+        sc[c][kk] = (c ? s_br : s_tl)[o];
+        tg[c][kk] = in ? (c ? tag_br : tag_tl)[(long)n * HW + ind] : 0.f;
+        cx[c][kk] = (int)(c ? x_br : x_tl)[o];
+        cy[c][kk] = (int)(c ? y_br : y_tl)[o];
+        ok[c][kk] = in;
+    }
+    if (tid == 0) s_nvalid = 0;
+    __syncthreads();
+    auto cand = [&](int f, unsigned& b) {
+        const int i = f / K, j = f - i * K;
+        b = __float_as_uint((sc[0][i] + sc[1][j]) * 0.5f);
+        return ok[0][i] && ok[1][j] && !(fabsf(tg[0][i] - tg[1][j]) > threshold) && !(cx[1][j] < cx[0][i]) &&
+               !(cy[1][j] < cy[0][i]);
+    };
+    unsigned mine = 0;
+    for (int f = tid; f < K * K; f += blockDim.x) {
+        unsigned b;
+        mine += cand(f, b) ? 1u : 0u;
+    }
+    if (mine) atomicAdd(&s_nvalid, mine);
+    __syncthreads();
+    const int nsel = min((int)s_nvalid, D);
+    __syncthreads();
+    if (nsel > 0) select_sorted_keys(cand, K * K, nsel, keys);
+    float* out = det + (long)n * D * 8;
+    for (int r = tid; r < D; r += blockDim.x) {
+        float row[8] = {0.f, 0.f, 0.f, 0.f, -1.f, 0.f, 0.f, 0.f};
+        if (r < nsel) {
+            const unsigned long long key = keys[r];
+            const int f = (int)(0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFu));
+            const int i = f / K, j = f - i * K;
+            row[0] = (float)cx[0][i]; row[1] = (float)cy[0][i]; row[2] = (float)cx[1][j]; row[3] = (float)cy[1][j];
+            row[4] = __uint_as_float((unsigned)(key >> 32)); row[5] = sc[0][i]; row[6] = sc[1][j];
+        }
+        *(float4*)(out + r * 8) = make_float4(row[0], row[1], row[2], row[3]);
+        *(float4*)(out + r * 8 + 4) = make_float4(row[4], row[5], row[6], row[7]);
+    }
+    if (tid == 0) nvalid[n] = nsel;
+}
+
+// ---------------------------------------------------------------- CornerNet: associative-embedding loss
+// embeddingLoss (models/losses/embeddings.py) with the pair mask its comment describes (a uint8 mask; with a bool mask
+// the reference's `mask + mask` stays bool, `.eq(2)` is false everywhere and push is 0: DESIGN §8f).  Per image b
+// with n valid slots, e_tl[k] / e_br[k] the tags at the slots' corner cells, m = (e_tl + e_br) / 2:
+//   pull = sum_{k valid} [(e_tl - m)^2 + (e_br - m)^2] / (n + 1e-4)
+//   push = sum_{i, j valid} [relu(1 - |m_i - m_j|) - 1 / (n + 1e-4)] / (n (n - 1) + 1e-4)      (diagonal included)
+// One workgroup per image; sums in double, written (not added) to the image's two accumulator slots, so the finalize
+// sums them in image order and nothing needs zeroing.  The per-slot gradients (torch's conventions: d|x|/dx = 0 at 0,
+// relu' = 0 at 0), already times w_pull / w_push, go to gs_tl / gs_br (N, K); the backward scatters them.
+constexpr int AE_MAXK = 64;
+constexpr int AE_THREADS = 256;
+
+__global__ __launch_bounds__(AE_THREADS) void corner_ae_fwd_kernel(const float* tl_tag, const float* br_tag, int HW,
+                                                                   const int64_t* tl_inds, const int64_t* br_inds,
+                                                                   const uint8_t* valid, int K, float w_pull,
+                                                                   float w_push, double* acc, float* gs_tl,
+                                                                   float* gs_br) {
+    __shared__ double et[AE_MAXK], eb[AE_MAXK], mm[AE_MAXK];
+    __shared__ int vd[AE_MAXK];
+    __shared__ double red[2][AE_THREADS / 64];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    if (tid < K) {
+        const long o = (long)b * K + tid;
+        const int64_t it = tl_inds[o], ib = br_inds[o];
+        const int v = valid[o] && it >= 0 && it < HW && ib >= 0 && ib < HW;
+        vd[tid] = v;
+        et[tid] = v ? (double)tl_tag[(long)b * HW + it] : 0.0;
+        eb[tid] = v ? (double)br_tag[(long)b * HW + ib] : 0.0;
+        mm[tid] = (et[tid] + eb[tid]) / 2;
+    }
+    __syncthreads();
+    int n = 0;
+    for (int k = 0; k < K; ++k) n += vd[k];
+    // the reference's normalisers are float32 whatever the tags' dtype (mask.sum().float() + 1e-4 and its reciprocal)
+    const float fn = (float)n;
+    const float dpull_f = fn + 1e-4f, dpush_f = (fn - 1.f) * fn + 1e-4f;
+    const double dpull = (double)dpull_f, dpush = (double)dpush_f, inv = (double)(1.f / dpull_f);
+    double pull = 0.0, push = 0.0;
+    if (tid < K && vd[tid]) {
+        const double a = et[tid] - mm[tid], c = eb[tid] - mm[tid];
+        pull = a * a / dpull + c * c / dpull;
+    }
+    for (int f = tid; f < K * K; f += blockDim.x) {
+        const int i = f / K, j = f - i * K;
+        if (!(vd[i] && vd[j])) continue;
+        push += (fmax(1.0 - fabs(mm[j] - mm[i]), 0.0) - inv) / dpush;
+    }
+    pull = wave_sum_d(pull);
+    push = wave_sum_d(push);
+    if ((tid & 63) == 0) { red[0][tid >> 6] = pull; red[1][tid >> 6] = push; }
+    __syncthreads();
+    if (tid == 0) {
+        double s0 = 0, s1 = 0;
+        for (int k = 0; k < AE_THREADS / 64; ++k) { s0 += red[0][k]; s1 += red[1][k]; }
+        acc[2 * b] = s0;
+        acc[2 * b + 1] = s1;
+    }
+    if (tid < K) {
+        double gt = 0.0, gb = 0.0;
+        if (vd[tid]) {
+            // pull: d/de_tl = 2 (e_tl - m) (1 - 1/2) + 2 (e_br - m) (-1/2) = (e_tl - m) - (e_br - m), over (n + 1e-4)
+            const double gp = ((et[tid] - mm[tid]) - (eb[tid] - mm[tid])) / dpull;
+            // push: m_i stands in the pairs (i, j) and (j, i); each gives -sign(m_i - m_j) where 1 - |..| > 0
+            double cnt = 0.0;
+            for (int j = 0; j < K; ++j) {
+                if (!vd[j]) continue;
+                const double d = mm[tid] - mm[j];
+                if (1.0 - fabs(d) > 0.0) cnt += d > 0.0 ? -1.0 : (d < 0.0 ? 1.0 : 0.0);
+            }
+            const double gm = 2.0 * cnt / dpush * 0.5;          // dm/de = 1/2 on both corners
+            gt = (double)w_pull * gp + (double)w_push * gm;
+            gb = -(double)w_pull * gp + (double)w_push * gm;
+        }
+        gs_tl[(long)b * K + tid] = (float)gt;
+        gs_br[(long)b * K + tid] = (float)gb;
+    }
+}
+
+// focal terms (FocalOnlyLossFn's finalize) + the embedding sums in image order -> out = [loss, focal x nfocal, w_pull
+// pull, w_push push], the focal backward factors; re-zeroes the focal replicas (consumer-cleared)
+__global__ void corner_ae_finalize_kernel(double* facc, int nfocal, const double* acc, int N, float w_pull, float w_push,
+                                          float* out, float* factors) {
+    if (threadIdx.x == 0) {
+        double total = 0.0;
+        for (int f = 0; f < nfocal; ++f) {
+            const float v = focal_finalize(facc, f, factors + f);
+            out[1 + f] = v;
+            total += v;
+        }
+        double pull = 0.0, push = 0.0;
+        for (int b = 0; b < N; ++b) { pull += acc[2 * b]; push += acc[2 * b + 1]; }
+        const float vp = w_pull * (float)pull, vq = w_push * (float)push;
+        out[1 + nfocal] = vp;
+        out[2 + nfocal] = vq;
+        out[0] = (float)(total + vp + vq);
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < nfocal * SCD_STAT_REPLICAS * FOCAL_ACC; i += blockDim.x) facc[i] = 0.0;
+}
+
+// backward: the two tag gradient maps (N, 1, H, W) written whole -- every pixel the sum, in slot order, of the slot
+// gradients of the valid slots that name it (two objects may share a corner cell), times the incoming gradient; zero
+// elsewhere.  One thread per pixel, so the sum is deterministic and no zero fill or atomic is needed.
+__global__ __launch_bounds__(256) void corner_ae_bwd_kernel(const float* gs_tl, const float* gs_br,
+                                                            const int64_t* tl_inds, const int64_t* br_inds,
+                                                            const uint8_t* valid, int K, int HW, const float* go,
+                                                            float* g_tl, float* g_br) {
+    __shared__ float gs[2][AE_MAXK];
+    __shared__ int ix[2][AE_MAXK];
+    const int b = blockIdx.y, tid = threadIdx.x;
+    if (tid < 2 * K) {
+        const int c = tid >= K, k = tid - c * K;
+        const long o = (long)b * K + k;
+        gs[c][k] = (c ? gs_br : gs_tl)[o];
+        const int64_t ind = (c ? br_inds : tl_inds)[o];
+        ix[c][k] = (valid[o] && ind >= 0 && ind < HW) ? (int)ind : -1;
+    }
+    __syncthreads();
+    const float s = go ? go[0] : 1.f;
+    for (int p = blockIdx.x * blockDim.x + tid; p < HW; p += gridDim.x * blockDim.x) {
+        float a = 0.f, c = 0.f;
+        for (int k = 0; k < K; ++k) {
+            if (ix[0][k] == p) a += gs[0][k];
+            if (ix[1][k] == p) c += gs[1][k];
+        }
+        g_tl[(long)b * HW + p] = a * s;
+        g_br[(long)b * HW + p] = c * s;
     }
 }
 
@@ -490,5 +700,47 @@ extern "C" int scd_decode_topk(const float* heat, int N, int H, int W, int K, co
     if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(decode_select_kernel, dim3(N), dim3(1024), 0, st, t, H * W, W, K, offset, od_off, regr, od_regr,
                        scores, inds, ys, xs, off_out, regr_out);
+    SCD_RETURN_LAUNCH();
+}
+
+extern "C" int scd_corner_pairs(const float* tl_scores, const int64_t* tl_inds, const int64_t* tl_ys,
+                                const int64_t* tl_xs, const float* br_scores, const int64_t* br_inds,
+                                const int64_t* br_ys, const int64_t* br_xs, const float* tl_tag, const float* br_tag,
+                                int N, int K, int HW, float threshold, int D, float* det, int* nvalid, void* stream) {
+    if (!tl_scores || !tl_inds || !tl_ys || !tl_xs || !br_scores || !br_inds || !br_ys || !br_xs || !tl_tag || !br_tag ||
+        !det || !nvalid)
+        return SCD_ERR_ARG;
+    if (N < 1 || K < 1 || K > PAIR_MAXK || HW < 1 || D < 1 || D > 1024 || D > K * K) return SCD_ERR_ARG;
+    hipLaunchKernelGGL(corner_pairs_kernel, dim3(N), dim3(1024), 0, (hipStream_t)stream, tl_scores, tl_inds, tl_ys, tl_xs,
+                       br_scores, br_inds, br_ys, br_xs, tl_tag, br_tag, K, HW, threshold, D, det, nvalid);
+    SCD_RETURN_LAUNCH();
+}
+
+extern "C" int scd_corner_ae_fwd(const float* tl_tag, const float* br_tag, int N, int HW, const int64_t* tl_inds,
+                                 const int64_t* br_inds, const uint8_t* valid, int K, float w_pull, float w_push,
+                                 double* focal_acc, int nfocal, double* ae_acc, float* gs_tl, float* gs_br, float* out,
+                                 float* factors, void* stream) {
+    if (!tl_tag || !br_tag || !tl_inds || !br_inds || !valid || !focal_acc || !ae_acc || !gs_tl || !gs_br || !out ||
+        !factors)
+        return SCD_ERR_ARG;
+    if (N < 1 || HW < 1 || (long)N * HW >= (1L << 31) || K < 1 || K > AE_MAXK || nfocal < 0) return SCD_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(corner_ae_fwd_kernel, dim3(N), dim3(AE_THREADS), 0, st, tl_tag, br_tag, HW, tl_inds, br_inds,
+                       valid, K, w_pull, w_push, ae_acc, gs_tl, gs_br);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(corner_ae_finalize_kernel, dim3(1), dim3(64), 0, st, focal_acc, nfocal, ae_acc, N, w_pull, w_push,
+                       out, factors);
+    SCD_RETURN_LAUNCH();
+}
+
+extern "C" int scd_corner_ae_bwd(const float* gs_tl, const float* gs_br, int N, int HW, const int64_t* tl_inds,
+                                 const int64_t* br_inds, const uint8_t* valid, int K, const float* go, float* g_tl,
+                                 float* g_br, void* stream) {
+    if (!gs_tl || !gs_br || !tl_inds || !br_inds || !valid || !g_tl || !g_br) return SCD_ERR_ARG;
+    if (N < 1 || N > 65535 || HW < 1 || (long)N * HW >= (1L << 31) || K < 1 || K > AE_MAXK) return SCD_ERR_ARG;
+    const int slices = std::max(1, std::min(64, cdiv(HW, 256)));
+    hipLaunchKernelGGL(corner_ae_bwd_kernel, dim3(slices, N), dim3(256), 0, (hipStream_t)stream, gs_tl, gs_br, tl_inds,
+                       br_inds, valid, K, HW, go, g_tl, g_br);
     SCD_RETURN_LAUNCH();
 }

@@ -130,6 +130,25 @@ __global__ __launch_bounds__(256) void render_center_kernel(const float* __restr
 // np.clip(v, 0, hi): NaN stays NaN
 __device__ __forceinline__ float clip_coord(float v, float hi) { return v < 0.f ? 0.f : (v > hi ? hi : v); }
 
+// the two corner cells of an object whose centre is on the map (the rule above), and which of them are drawn
+struct CornerCells {
+    int x0, y0, x1, y1, in0, in1;
+};
+
+__device__ __forceinline__ CornerCells corner_cells(const float* o, int H) {
+    const float hi = (float)(H - 1);
+    const float dx = rintf(fabsf(o[4])), dy = rintf(o[6]);
+    const float x0 = clip_coord(o[0] - dx, hi), y0 = clip_coord(o[1] - dy, hi);
+    const float x1 = clip_coord(o[0] + dx, hi), y1 = clip_coord(o[1] + dy, hi);
+    CornerCells c;
+    // finite after the clip means not NaN, and then inside [0, H - 1]
+    c.in0 = x0 == x0 && y0 == y0;
+    c.in1 = x1 == x1 && y1 == y1;
+    c.x0 = c.in0 ? (int)x0 : 0; c.y0 = c.in0 ? (int)y0 : 0;
+    c.x1 = c.in1 ? (int)x1 : 0; c.y1 = c.in1 ? (int)y1 : 0;
+    return c;
+}
+
 __global__ __launch_bounds__(256) void render_corner_kernel(const float* __restrict__ locs, const int* __restrict__ counts,
                                                             int K, int H, float thr, float* __restrict__ heat,
                                                             float* __restrict__ tl, float* __restrict__ br,
@@ -150,13 +169,9 @@ __global__ __launch_bounds__(256) void render_corner_kernel(const float* __restr
             double den;
             splat_shape(o, thr, roi, den);
             splat_window(ct, x, y, roi, den, H);
-            const float hi = (float)(H - 1);
-            const float dx = rintf(fabsf(o[4])), dy = rintf(o[6]);
-            const float x0 = clip_coord(o[0] - dx, hi), y0 = clip_coord(o[1] - dy, hi);
-            const float x1 = clip_coord(o[0] + dx, hi), y1 = clip_coord(o[1] + dy, hi);
-            // finite after the clip means not NaN, and then inside [0, H - 1]
-            if (x0 == x0 && y0 == y0) { c0.inside = 1; splat_window(c0, (int)x0, (int)y0, roi, den, H); }
-            if (x1 == x1 && y1 == y1) { c1.inside = 1; splat_window(c1, (int)x1, (int)y1, roi, den, H); }
+            const CornerCells cc = corner_cells(o, H);
+            if (cc.in0) { c0.inside = 1; splat_window(c0, cc.x0, cc.y0, roi, den, H); }
+            if (cc.in1) { c1.inside = 1; splat_window(c1, cc.x1, cc.y1, roi, den, H); }
         }
         box[0][k] = ct; box[1][k] = c0; box[2][k] = c1;
         if (blockIdx.y == 0 && blockIdx.z == 0) write_rows(o, n, k, K, cnt, H, ct.inside, mask, regr, inds);
@@ -169,6 +184,28 @@ __global__ __launch_bounds__(256) void render_corner_kernel(const float* __restr
             hm[p] = splat_pixel(box[m], cnt, px, py);
         }
     }
+}
+
+// ---- scd_corner_tag_inds: the cells an embedding loss gathers its tags at ---------------------------------------------
+// Per slot the flat cell (y * H + x) of the two corners render_corner_kernel draws, from the same center_cell /
+// corner_cells; valid exactly when it draws both (slot below the count, centre on the map, both corners finite), else
+// both indices are 0.
+__global__ void corner_tag_inds_kernel(const float* __restrict__ locs, const int* __restrict__ counts, int B, int K, int H,
+                                       int64_t* __restrict__ tl_inds, int64_t* __restrict__ br_inds,
+                                       uint8_t* __restrict__ valid) {
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= B * K) return;
+    const int n = s / K, k = s - n * K;
+    const float* o = locs + (size_t)s * 8;
+    int x, y, ok = center_cell(o, k, min(counts[n], K), H, x, y);
+    CornerCells cc{0, 0, 0, 0, 0, 0};
+    if (ok) {
+        cc = corner_cells(o, H);
+        ok = cc.in0 && cc.in1;
+    }
+    tl_inds[s] = ok ? (int64_t)cc.y0 * H + cc.x0 : 0;
+    br_inds[s] = ok ? (int64_t)cc.y1 * H + cc.x1 : 0;
+    valid[s] = (uint8_t)ok;
 }
 
 // ---- scd_pack_locs: the label half of a training batch built from a device-resident archive -------------------------
@@ -307,4 +344,14 @@ extern "C" int scd_render_corner_targets(const float* locs, const int* counts, i
                                          void* stream) {
     return scd_render_corner_targets_split(locs, counts, B, K, H, threshold, heat, tl, br, mask, regr, inds,
                                            SCD_CORNER_SPLIT_DEFAULT, stream);
+}
+
+extern "C" int scd_corner_tag_inds(const float* locs, const int* counts, int B, int K, int size, int64_t* tl_inds,
+                                   int64_t* br_inds, uint8_t* valid, void* stream) {
+    if (!locs || !counts || !tl_inds || !br_inds || !valid) return SCD_ERR_ARG;
+    if (B < 1 || K < 1 || K > MAXOBJ || size < 1 || (long)size * size >= (1L << 31) || (long)B * K >= (1L << 28))
+        return SCD_ERR_ARG;
+    hipLaunchKernelGGL(corner_tag_inds_kernel, dim3(cdiv((long)B * K, 256)), dim3(256), 0, (hipStream_t)stream, locs,
+                       counts, B, K, size, tl_inds, br_inds, valid);
+    SCD_RETURN_LAUNCH();
 }

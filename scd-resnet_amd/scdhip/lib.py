@@ -115,6 +115,9 @@ SIGNATURES = {
     "scd_heads_keep_map": (I, [P, I, I, I, P, I, P, P]),
     "scd_centernet_loss_fwd": (I, [P, P, L, P, I, P, I, I, I, P, P, P, I, I, I, I, P, P, P, P, P, P, P, P]),
     "scd_centernet_loss_bwd_scale": (I, [P, L, I, I, P, I, P, I, P, I, P, P, P]),
+    "scd_corner_ae_fwd": (I, [P, P, I, I, P, P, P, I, F, F, P, I, P, P, P, P, P, P]),
+    "scd_corner_ae_bwd": (I, [P, P, I, I, P, P, P, I, P, P, P, P]),
+    "scd_corner_pairs": (I, [P, P, P, P, P, P, P, P, P, P, I, I, I, F, I, P, P, P]),
     "scd_decode_workspace": (c_size_t, [I, I]),
     "scd_decode_topk": (I, [P, I, I, I, I, P, I, P, I, P, P, P, P, P, P, P, P]),
     "scd_augment_workspace": (c_size_t, [I]),
@@ -140,6 +143,7 @@ SIGNATURES = {
     "scd_render_center_targets": (I, [P, P, I, I, I, F, P, P, P, P, P]),
     "scd_render_corner_targets": (I, [P, P, I, I, I, F, P, P, P, P, P, P, P]),
     "scd_render_corner_targets_split": (I, [P, P, I, I, I, F, P, P, P, P, P, P, I, P]),
+    "scd_corner_tag_inds": (I, [P, P, I, I, I, P, P, P, P]),
     "scd_cpool_fwd": (I, [I, I, P, P, P, I, I, I, I, P]),
     "scd_cpool_bwd": (I, [I, I, P, P, P, I, I, I, I, P]),
     "scd_nms": (I, [P, L, I, I, I, P, P]),

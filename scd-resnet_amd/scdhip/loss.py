@@ -97,13 +97,7 @@ class FocalOnlyLossFn(torch.autograd.Function):
         dev = heats[0].device
         s = ops.stream()
         facc = _acc_buffer(dev, "focal%d" % n, n * L.STAT_REPLICAS * 4)
-        grads = []
-        for i, (h, g) in enumerate(zip(heats, gts)):
-            h = h.contiguous()
-            gh = torch.empty_like(h)
-            L.call("scd_focal_fwd", ops.ptr(h), ops.ptr(g.float().contiguous()), h.numel(), ops.ptr(gh),
-                   ops.ptr(facc[i * L.STAT_REPLICAS * 4:]), s)
-            grads.append(gh)
+        grads = _focal_fwd(heats, gts, facc, s)
         out = torch.empty(1 + n, device=dev)
         factors = torch.empty(n, device=dev)
         L.call("scd_centernet_loss_finalize", ops.ptr(facc), n, 0, 0, ctypes_float2(0.0, 0.0), ops.ptr(out),
@@ -120,10 +114,79 @@ class FocalOnlyLossFn(torch.autograd.Function):
     def backward(ctx, gl, gstats):
         factors, *grads = ctx.saved_tensors
         gl = gl.contiguous() if gl is not None else torch.ones(1, device=factors.device)
-        s = ops.stream()
-        for i, g in enumerate(grads):
-            L.call("scd_scale_by_device", ops.ptr(g), g.numel(), ops.ptr(factors), i, ops.ptr(gl), s)
+        _focal_scale(grads, factors, gl, ops.stream())
         return tuple(grads) + (None,) * len(grads)
+
+
+def _focal_fwd(heats, gts, facc, s):
+    """scd_focal_fwd per map: its sums into map i's replicas of `facc`; returns the unscaled gradients."""
+    grads = []
+    for i, (h, g) in enumerate(zip(heats, gts)):
+        h = h.contiguous()
+        gh = torch.empty_like(h)
+        L.call("scd_focal_fwd", ops.ptr(h), ops.ptr(g.float().contiguous()), h.numel(), ops.ptr(gh),
+               ops.ptr(facc[i * L.STAT_REPLICAS * 4:]), s)
+        grads.append(gh)
+    return grads
+
+
+def _focal_scale(grads, factors, gl, s):
+    """The saved focal gradients times their finalize factor and the incoming gradient, in place."""
+    for i, g in enumerate(grads):
+        L.call("scd_scale_by_device", ops.ptr(g), g.numel(), ops.ptr(factors), i, ops.ptr(gl), s)
+
+
+class CornerNetAELossFn(torch.autograd.Function):
+    """CornerNetLoss of cornerNetLegacy.py:558-640 on one output stack, without its regression terms: the three focal
+    losses of FocalOnlyLossFn + w_pull * pull + w_push * push of embeddingLoss (models/losses/embeddings.py, with the
+    pair mask a uint8 mask gives it; scd_corner_ae_fwd).  tl_inds / br_inds (N,K) int64 cells and valid (N,K) come
+    from ops.corner_tag_inds.  Returns (loss[0:1], stats = [focal heat, focal tl, focal br, w_pull pull, w_push push])."""
+
+    @staticmethod
+    def forward(ctx, heat, tl, br, tl_tag, br_tag, gt_heat, gt_tl, gt_br, tl_inds, br_inds, valid, w_pull, w_push):
+        ops._need_gpu(heat, tl_tag, tl_inds)
+        dev = heat.device
+        s = ops.stream()
+        N, _, H, W = tl_tag.shape
+        K = tl_inds.shape[1]
+        facc = _acc_buffer(dev, "focal3", 3 * L.STAT_REPLICAS * 4)
+        grads = _focal_fwd((heat, tl, br), (gt_heat, gt_tl, gt_br), facc, s)
+        tl_tag, br_tag = tl_tag.float().contiguous(), br_tag.float().contiguous()
+        tl_inds, br_inds = tl_inds.to(torch.int64).contiguous(), br_inds.to(torch.int64).contiguous()
+        valid = valid.contiguous()
+        valid = valid.view(torch.uint8) if valid.dtype == torch.bool else valid.to(torch.uint8)
+        acc = _acc_buffer(dev, "ae", 2 * N)
+        gs = torch.empty(2, N, K, device=dev)
+        out = torch.empty(6, device=dev)
+        factors = torch.empty(3, device=dev)
+        L.call("scd_corner_ae_fwd", ops.ptr(tl_tag), ops.ptr(br_tag), N, H * W, ops.ptr(tl_inds), ops.ptr(br_inds),
+               ops.ptr(valid), K, float(w_pull), float(w_push), ops.ptr(facc), 3, ops.ptr(acc), ops.ptr(gs[0]),
+               ops.ptr(gs[1]), ops.ptr(out), ops.ptr(factors), s)
+        ctx.save_for_backward(factors, gs, tl_inds, br_inds, valid, *grads)
+        ctx.tag_shape = tl_tag.shape
+        ops.clear_sparse_grads()          # a new loss: earlier certificates are consumed or stale
+        stats = out[1:6]
+        ctx.mark_non_differentiable(stats)
+        ctx.set_materialize_grads(False)  # as CenterNetLossFn: no zeros tensor for the statistics
+        return out[0:1], stats
+
+    @staticmethod
+    def backward(ctx, gl, gstats):
+        factors, gs, tl_inds, br_inds, valid, *grads = ctx.saved_tensors
+        gl = gl.contiguous() if gl is not None else torch.ones(1, device=factors.device)
+        s = ops.stream()
+        _focal_scale(grads, factors, gl, s)
+        N, _, H, W = ctx.tag_shape
+        # two storages: each tag head's gradient carries its own certificate
+        g_tl = torch.empty(ctx.tag_shape, device=factors.device)
+        g_br = torch.empty(ctx.tag_shape, device=factors.device)
+        L.call("scd_corner_ae_bwd", ops.ptr(gs[0]), ops.ptr(gs[1]), N, H * W, ops.ptr(tl_inds), ops.ptr(br_inds),
+               ops.ptr(valid), tl_inds.shape[1], ops.ptr(gl), ops.ptr(g_tl), ops.ptr(g_br), s)
+        # zero outside the gathered pixels; a pixel named by two slots holds their sum, which the sparse heads backward
+        # reads once (the first slot naming it), and the invalid slots' pixel 0 holds zero or a valid slot's gradient
+        ops.certify_sparse_grad(g_tl, tl_inds)
+        ops.certify_sparse_grad(g_br, br_inds)
+        return (*grads, g_tl, g_br) + (None,) * 8
 
 
 _ACC = {}

@@ -1630,6 +1630,49 @@ def render_corner_targets(locs, counts, size=128, threshold=0.5, split=None):
     return [heat, mask, regr, tl, br, inds]
 
 
+def corner_tag_inds(locs, counts, size=128):
+    """The cells CornerNet's embedding loss gathers its tags at (scd_corner_tag_inds), from the rows
+    render_corner_targets renders: locs (B,K,8) fp32, counts (B,) -> (tl_inds, br_inds (B,K) int64 = y * size + x of
+    the slot's corner cells, valid (B,K) bool: the renderer draws both corners of the slot; an invalid slot's indices
+    are 0)."""
+    _need_gpu(locs)
+    locs = locs.float().contiguous()
+    counts = counts.to(device=locs.device, dtype=torch.int32).contiguous()
+    B, K, _ = locs.shape
+    tl_inds = torch.empty(B, K, dtype=torch.int64, device=locs.device)
+    br_inds = torch.empty_like(tl_inds)
+    valid = torch.empty(B, K, dtype=torch.bool, device=locs.device)
+    L.call("scd_corner_tag_inds", ptr(locs), ptr(counts), B, K, size, ptr(tl_inds), ptr(br_inds), ptr(valid), stream())
+    return tl_inds, br_inds, valid
+
+
+CORNER_PAIRS_MAX_K = 128        # scd_corner_pairs: corners per map
+CORNER_PAIRS_MAX_COUNT = 1024   # ... and rows per image (the sort buffer of the top-K select)
+
+
+def corner_pairs(tl, br, tl_tag, br_tag, threshold=1.0, count=1000):
+    """decodeCornerNet's pairing (cornerNetLegacy.py:332-446, one category) on the GPU (scd_corner_pairs, one launch):
+    tl, br = (scores, inds, ys, xs) of decode_topk on the two corner maps, tl_tag / br_tag (N,1,H,W) tag maps ->
+    (det (N,D,8) f32, nvalid (N,) i32), D = min(count, K*K).  Rows [x_tl, y_tl, x_br, y_br, score, s_tl, s_br, 0] by
+    score descending then flat index i*K + j ascending; rows past nvalid[b] have score -1 and zeros."""
+    _need_gpu(tl[0], tl_tag)
+    N, K = tl[0].shape
+    if K > CORNER_PAIRS_MAX_K or count > CORNER_PAIRS_MAX_COUNT or count < 1:
+        raise ValueError("corner_pairs: K <= %d and 1 <= count <= %d, got K = %d, count = %d" % (
+            CORNER_PAIRS_MAX_K, CORNER_PAIRS_MAX_COUNT, K, count))
+    D = min(count, K * K)
+    dev = tl_tag.device
+    HW = tl_tag.shape[-2] * tl_tag.shape[-1]
+    if tl_tag.numel() != N * HW or br_tag.numel() != N * HW:
+        raise ValueError("corner_pairs: tag maps of shape (N,1,H,W) with N = %d" % N)
+    args = [t.float().contiguous() if i % 4 == 0 else t.to(torch.int64).contiguous() for i, t in enumerate((*tl, *br))]
+    tags = [tl_tag.float().contiguous(), br_tag.float().contiguous()]
+    det = torch.empty(N, D, 8, device=dev)
+    nvalid = torch.empty(N, dtype=torch.int32, device=dev)
+    L.call("scd_corner_pairs", *[ptr(a) for a in args], ptr(tags[0]), ptr(tags[1]), N, K, HW, float(threshold), D,
+           ptr(det), ptr(nvalid), stream())
+    return det, nvalid
+
 
 CEVAL_STREAMS = ("iou", "score", "ortho", "ioucenter", "iouoffsetwo", "iouoffset", "aemaj", "aemin", "aerad")
 _CEVAL_STREAM_MASK = (0, 0, 1, 2, 3, 4, 1, 1, 1)

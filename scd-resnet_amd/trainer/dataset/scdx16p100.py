@@ -143,8 +143,21 @@ def _render_targets(locs, counts):
     same)."""
     from configuration import defaultConfig
     from scdhip import ops
+    if defaultConfig.cornerEmbeddings and not defaultConfig.cornerTargets:
+        raise RuntimeError("scdx16p100: the configuration key cornerEmbeddings needs cornerTargets on")
     render = ops.render_corner_targets if defaultConfig.cornerTargets else ops.render_center_targets
     return render(locs, counts, HEATMAPSIZE, THRESHOLDIOU)
+
+
+def _corner_layout(ys, locs, counts):
+    """A training batch's ys from _render_targets' list: its first five entries, and with the configuration key
+    cornerEmbeddings on the corner cells and slots of the same device rows behind them (scd_corner_tag_inds):
+    [heat, mask, regr, tl, br, tl_inds, br_inds, valid]."""
+    from configuration import defaultConfig
+    if not defaultConfig.cornerEmbeddings:
+        return ys[:5]
+    from scdhip import ops
+    return ys[:5] + list(ops.corner_tag_inds(locs, counts, HEATMAPSIZE))
 
 
 def splitOrder(count, dataSplit=None, ratio=ARGUMENTRATIO, partition=PARTITION, subset=TRAINSUBSET):
@@ -199,7 +212,7 @@ class SCD(Dataset):
         from configuration import defaultConfig
         from scdhip import ops
         ids = self.dataProfile['validation'][:REALTIMETEST]
-        xs, heat, mask, regr, locs, inds, tl, br = [], [], [], [], [], [], [], []
+        xs, heat, mask, regr, locs, inds, tl, br, tags = [], [], [], [], [], [], [], [], ([], [], [])
         self.validObjNum = [int(len(self.bounds[i])) for i in ids]
         for c0 in range(0, len(ids), chunk):
             part = ids[c0:c0 + chunk]
@@ -210,6 +223,9 @@ class SCD(Dataset):
             h, m, r, *corners, ind = _render_targets(L, torch.from_numpy(n).to(self.device))
             for kept, c in zip((tl, br), corners):      # cornerTargets on
                 kept.append(c)
+            if defaultConfig.cornerEmbeddings:
+                for kept, c in zip(tags, ops.corner_tag_inds(L, torch.from_numpy(n).to(self.device), HEATMAPSIZE)):
+                    kept.append(c)
             # validation masks every stored object (scdx16p100.py:219-220)
             m = torch.arange(MAXTAGLEN, device=self.device)[None, :] < torch.from_numpy(n).to(self.device)[:, None]
             heat.append(h); mask.append(m); regr.append(r); locs.append(L); inds.append(ind)
@@ -220,11 +236,14 @@ class SCD(Dataset):
                    cat(regr, (0, MAXTAGLEN, 6)), cat(locs, (0, MAXTAGLEN, 8)), self.validObjNum]}
         if defaultConfig.cornerTargets:
             self.validation["corners"] = [cat(t, (0, 1, HEATMAPSIZE, HEATMAPSIZE)) for t in (tl, br)]
+        if defaultConfig.cornerEmbeddings:
+            self.validation["tags"] = [cat(t, (0, MAXTAGLEN)) for t in tags]
 
     def getValidationSet(self):
         """scdx16p100.py:381-414 (REALTIMETEST positions in validationBatchSize slices; empty slices of a small
         archive are dropped).  With the configuration key cornerTargets on every slice carries CornerNet's layout
-        ys = [heat, mask, regr, tl, br], the corner maps _buildValidation kept."""
+        ys = [heat, mask, regr, tl, br], the corner maps _buildValidation kept; with cornerEmbeddings on too, the
+        three (., K) tensors tl_inds, br_inds, valid behind them."""
         from configuration import defaultConfig
         v = self.validation
         length = REALTIMETEST
@@ -233,7 +252,14 @@ class SCD(Dataset):
             if "corners" not in v:
                 raise RuntimeError("scdx16p100: cornerTargets was off when this dataset was built, its validation set "
                                    "holds no corner maps")
-            part = (lambda s: [v['ys'][0][s], v['ys'][1][s], v['ys'][2][s], v['corners'][0][s], v['corners'][1][s]])
+            extra = []
+            if defaultConfig.cornerEmbeddings:
+                if "tags" not in v:
+                    raise RuntimeError("scdx16p100: cornerEmbeddings was off when this dataset was built, its "
+                                       "validation set holds no corner cells")
+                extra = v["tags"]
+            part = (lambda s: [v['ys'][0][s], v['ys'][1][s], v['ys'][2][s], v['corners'][0][s], v['corners'][1][s]]
+                    + [t[s] for t in extra])
         else:
             part = (lambda s: [v['ys'][0][s], v['ys'][1][s], v['ys'][2][s], v['ys'][3][s], v['ys'][4][s],
                                v['xs'][1][s]])
@@ -322,7 +348,8 @@ class SCD(Dataset):
         scd_render_center_targets): {"xs": [(B,1,S,S)], "ys": [heat, mask, regr, inds]} on the device, the
         reference's __getitem__ stacked over `indices` (positions in the shuffled order).  With the configuration's
         rotateAugmentation > 0, scd_rotate_tiles and rotateLocs follow the augmentation and the flips.  With its
-        cornerTargets on, ys = [heat, mask, regr, tl, br] from scd_render_corner_targets on the same rows."""
+        cornerTargets on, ys = [heat, mask, regr, tl, br] from scd_render_corner_targets on the same rows, and with
+        cornerEmbeddings on too, [..., tl_inds, br_inds, valid] from scd_corner_tag_inds on them (_corner_layout)."""
         from configuration import defaultConfig
         from scdhip import ops
         dev = device or self.device
@@ -341,8 +368,8 @@ class SCD(Dataset):
             xs = ops.rotate_tiles(xs, angles)
             rows = [self.rotateLocs(r, a) for r, a in zip(rows, angles)]
         l, n = _pack_locs(rows, trunc=True)
-        ys = _render_targets(torch.from_numpy(l).to(dev), torch.from_numpy(n).to(dev))
-        return {"xs": [xs], "ys": ys[:5]}
+        l, n = torch.from_numpy(l).to(dev), torch.from_numpy(n).to(dev)
+        return {"xs": [xs], "ys": _corner_layout(_render_targets(l, n), l, n)}
 
     # ------------------------------------------------------------------ device-resident archive
     def _buildResident(self, dev, chunk=256):
@@ -377,7 +404,8 @@ class SCD(Dataset):
         """gpu_batch from the device-resident archive: the same draws in the same order, one upload of the batch's
         ids, flips, jitter factors and rotation coefficients, then scd_augment_tiles_indexed, scd_rotate_tiles (when
         rotateAugmentation > 0), scd_pack_locs and scd_render_center_targets (scd_render_corner_targets on the same
-        device rows when cornerTargets is on).  No host tile or label is read and
+        device rows when cornerTargets is on, and scd_corner_tag_inds on them when cornerEmbeddings is on too).  No
+        host tile or label is read and
         there is no explicit synchronise (the one upload, from pageable memory, is a blocking copy on the current
         stream, as every upload of the host path is)."""
         from scdhip import ops
@@ -415,7 +443,7 @@ class SCD(Dataset):
             cs = views[1].view(torch.float32).view(B, 2)
         locs, counts = ops.pack_locs(res["rows"], res["offsets"], dids, dflips, size=HEATMAPSIZE, K=MAXTAGLEN,
                                      trunc=True, cs=cs)
-        return {"xs": [xs], "ys": _render_targets(locs, counts)[:5]}
+        return {"xs": [xs], "ys": _corner_layout(_render_targets(locs, counts), locs, counts)}
 
     def __getitem__(self, index):
         b = self.gpu_batch([index])
