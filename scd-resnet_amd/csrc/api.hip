@@ -6,37 +6,10 @@
 //   L1LossMask / smoothL1LossMask  models/losses/regression.py:28-44  scd_masked_l1_fwd (+ finalize)
 // Forward passes also write the per-element gradient; the normalisers stay on the device (finalize factors), so
 // no entry point synchronises with the host.
-#include <algorithm>
-
-#include "scd_common.h"
+#define BLOCK_OPS_FP
+#include "block_ops.h"
 
 namespace {
-
-inline int ew_blocks(long n) { return (int)std::min<long>(4096, std::max<long>(1, (n + 255) / 256)); }
-
-// out = x where x equals its k x k neighbourhood max (padding -inf), else 0 -- heat * (maxpool(heat) == heat)
-__global__ void nms_kernel(const float* x, long planes, int H, int W, int k, float* out) {
-    const long total = planes * H * W;
-    const int r = (k - 1) / 2;
-    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-        const long pl = i / ((long)H * W);
-        const int rem = (int)(i - pl * H * W);
-        const int y = rem / W, xx = rem - (rem / W) * W;
-        const float* hp = x + pl * H * W;
-        const float v = hp[rem];
-        float m = -INFINITY;
-        for (int dy = -r; dy <= k - 1 - r; ++dy) {
-            const int yy = y + dy;
-            if ((unsigned)yy >= (unsigned)H) continue;
-            for (int dx = -r; dx <= k - 1 - r; ++dx) {
-                const int xc = xx + dx;
-                if ((unsigned)xc >= (unsigned)W) continue;
-                m = fmaxf(m, hp[yy * W + xc]);
-            }
-        }
-        out[i] = v * (m == v ? 1.f : 0.f);
-    }
-}
 
 // order-preserving key of a float (larger float -> larger unsigned)
 __device__ __forceinline__ unsigned fkey(float f) {
@@ -49,6 +22,8 @@ __device__ __forceinline__ float fkey_inv(unsigned k) {
 
 // one 1024-thread block per row: radix-select the K-th largest key, collect the larger ones and the lowest-index
 // ties, bitonic sort by (value desc, index asc); then the reference's category / index / y / x split
+// (select_sorted_keys of loss_decode.hip written out on fkey(v[i]) with 64-bit indices: its own copy, through the
+// template with a candidate functor the kernel took 55 more instructions and ran 2 % slower)
 __global__ __launch_bounds__(1024) void topk_kernel(const float* s, long n, int K, int HW, int W, float* scores,
                                                     int64_t* inds, int* cats, float* ys, float* xs) {
     __shared__ unsigned hist[256];
@@ -148,43 +123,13 @@ __global__ __launch_bounds__(1024) void topk_kernel(const float* s, long n, int 
     }
 }
 
-constexpr int FOCAL_ACC = 4;     // posL, negL, npos, pad (the layout scd_centernet_loss_finalize reads)
-
 // focal.py:25-53 on probabilities p (no sigmoid / clamp here: the caller's clampSigmoid did that): per element
 // dL/dp up to the normaliser, and the posL / negL / #pos sums into fp64 replica slots
 __global__ void focal_prob_kernel(const float* p, const float* gt, long n, float* g, double* acc) {
     float posl = 0.f, negl = 0.f, npos = 0.f;
-    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-        const float pc = p[i], t = gt[i];
-        float d = 0.f;
-        if (t == 1.f) {
-            const float om = 1.f - pc;
-            const float lg = logf(pc);
-            posl += lg * (om * om);
-            npos += 1.f;
-            d = om * om / pc - 2.f * om * lg;
-        } else if (t < 1.f) {
-            const float om = 1.f - t;
-            const float w = (om * om) * (om * om);
-            const float l1m = logf(1.f - pc);
-            negl += l1m * (pc * pc) * w;
-            d = w * (-(pc * pc) / (1.f - pc) + 2.f * pc * l1m);
-        }
-        g[i] = d;
-    }
-    __shared__ double red[3][4];
-    double a = wave_sum_d((double)posl), b = wave_sum_d((double)negl), c = wave_sum_d((double)npos);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) { red[0][w] = a; red[1][w] = b; red[2][w] = c; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double* dst = acc + (long)(blockIdx.x % SCD_STAT_REPLICAS) * FOCAL_ACC;
-        double s0 = 0, s1 = 0, s2 = 0;
-        for (int k = 0; k < (int)(blockDim.x / 64); ++k) { s0 += red[0][k]; s1 += red[1][k]; s2 += red[2][k]; }
-        atomic_add_f64(dst + 0, s0);
-        atomic_add_f64(dst + 1, s1);
-        atomic_add_f64(dst + 2, s2);
-    }
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
+        g[i] = focal_term(p[i], gt[i], posl, negl, npos);
+    focal_accumulate(posl, negl, npos, acc);
 }
 
 // regression.py:28-44 on gathered (rows, C) tensors: masked |d| (or smooth-L1, beta 1) summed, the mask count, and
@@ -212,16 +157,10 @@ __global__ void masked_l1_kernel(const float* r, const float* t, const uint8_t* 
             g[e] = gv;
         }
     }
-    __shared__ double red[2][4];
-    double a = wave_sum_d((double)s), b = wave_sum_d((double)cnt);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) { red[0][w] = a; red[1][w] = b; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double s0 = 0, s1 = 0;
-        for (int k = 0; k < (int)(blockDim.x / 64); ++k) { s0 += red[0][k]; s1 += red[1][k]; }
-        atomic_add_f64(acc + 0, s0);
-        atomic_add_f64(acc + 1, s1);
+    double a = (double)s, b = (double)cnt;
+    if (block_sums_d<4>(a, b, blockDim.x / 64)) {
+        atomic_add_f64(acc + 0, a);
+        atomic_add_f64(acc + 1, b);
     }
 }
 
@@ -229,8 +168,8 @@ __global__ void masked_l1_kernel(const float* r, const float* t, const uint8_t* 
 
 extern "C" int scd_nms(const float* x, long planes, int H, int W, int k, float* out, void* stream) {
     if (planes < 0 || H < 1 || W < 1 || k < 1 || k % 2 == 0) return SCD_ERR_ARG;
-    hipLaunchKernelGGL(nms_kernel, dim3(ew_blocks(planes * H * W)), dim3(256), 0, (hipStream_t)stream, x, planes, H, W,
-                       k, out);
+    hipLaunchKernelGGL(nms_kernel<NmsProduct>, dim3(ew_blocks(planes * H * W)), dim3(256), 0, (hipStream_t)stream, x,
+                       planes, H, W, k, out);
     SCD_RETURN_LAUNCH();
 }
 

@@ -50,16 +50,9 @@ __global__ __launch_bounds__(AUG_THREADS) void aug_stats_kernel(const float* __r
         s1 += (double)v.x + (double)v.y + (double)v.z + (double)v.w;
         s2 += (double)v.x * v.x + (double)v.y * v.y + (double)v.z * v.z + (double)v.w * v.w;
     }
-    __shared__ double red[2][AUG_THREADS / 64];
-    s1 = wave_sum_d(s1);
-    s2 = wave_sum_d(s2);
-    if ((tid & 63) == 0) { red[0][tid >> 6] = s1; red[1][tid >> 6] = s2; }
-    __syncthreads();
-    if (tid == 0) {
-        double a = 0.0, c = 0.0;
-        for (int w = 0; w < AUG_THREADS / 64; ++w) { a += red[0][w]; c += red[1][w]; }
-        part[((long)b * AUG_SLICES + s) * 2] = a;
-        part[((long)b * AUG_SLICES + s) * 2 + 1] = c;
+    if (block_sums_d<AUG_THREADS / 64>(s1, s2, AUG_THREADS / 64)) {
+        part[((long)b * AUG_SLICES + s) * 2] = s1;
+        part[((long)b * AUG_SLICES + s) * 2 + 1] = s2;
     }
 }
 

@@ -1,51 +1,16 @@
 // CenterNet loss (focal.py:25-53, regression.py:37-44, centerNetOffset.py:182-217) and
 // decode (centerNetOffset.py:219-251, utility.py:87-118) on device, with no host syncs:
 // normalisers (#pos, #mask) stay in device memory and are consumed by the backward scale.
-#include <algorithm>
-
-#include "scd_common.h"
+#define BLOCK_OPS_FP
+#include "block_ops.h"
 
 namespace {
 
-constexpr int FOCAL_ACC = 4;     // posL, negL, npos, pad
-
 __global__ void focal_fwd_kernel(const float* x, const float* gt, long n, float* g, double* acc) {
     float posl = 0.f, negl = 0.f, npos = 0.f;
-    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-        const float xi = x[i], t = gt[i];
-        const float p = 1.f / (1.f + expf(-xi));
-        const bool pass = (p >= 1e-4f) && (p <= 1.f - 1e-4f);
-        const float pc = fminf(fmaxf(p, 1e-4f), 1.f - 1e-4f);
-        float dterm = 0.f;
-        if (t == 1.f) {
-            const float om = 1.f - pc;
-            const float lg = logf(pc);
-            posl += lg * (om * om);
-            npos += 1.f;
-            dterm = om * om / pc - 2.f * om * lg;
-        } else if (t < 1.f) {
-            const float om = 1.f - t;
-            const float w = (om * om) * (om * om);
-            const float l1m = logf(1.f - pc);
-            negl += l1m * (pc * pc) * w;
-            dterm = w * (-(pc * pc) / (1.f - pc) + 2.f * pc * l1m);
-        }
-        g[i] = pass ? dterm * p * (1.f - p) : 0.f;
-    }
-    __shared__ double red[3][4];
-    double a = wave_sum_d((double)posl), b = wave_sum_d((double)negl), c = wave_sum_d((double)npos);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) { red[0][w] = a; red[1][w] = b; red[2][w] = c; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double* dst = acc + (long)(blockIdx.x % SCD_STAT_REPLICAS) * FOCAL_ACC;
-        const int nw = blockDim.x / 64;
-        double s0 = 0, s1 = 0, s2 = 0;
-        for (int k = 0; k < nw; ++k) { s0 += red[0][k]; s1 += red[1][k]; s2 += red[2][k]; }
-        atomic_add_f64(dst + 0, s0);
-        atomic_add_f64(dst + 1, s1);
-        atomic_add_f64(dst + 2, s2);
-    }
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
+        g[i] = focal_logit_term(x[i], gt[i], posl, negl, npos);
+    focal_accumulate(posl, negl, npos, acc);
 }
 
 // masked L1 on features gathered at inds (NCHW fp32).  g must be zero on entry.
@@ -57,6 +22,7 @@ __global__ void l1_gather_kernel(const float* feat, int N, int C, int HW, const 
         if (!mask[i]) continue;
         cnt += 1.f;
         const long ind = inds[i];
+        // (the same loop as centernet_loss_b_kernel's: as a shared function it cost this kernel 2 instructions)
         for (int c = 0; c < C; ++c) {
             const long fi = ((long)n * C + c) * HW + ind;
             const float d = feat[fi] - target[(long)i * tstride + toff + c];
@@ -65,16 +31,10 @@ __global__ void l1_gather_kernel(const float* feat, int N, int C, int HW, const 
             if (sg != 0.f) atomic_add_f32(g + fi, sg);
         }
     }
-    __shared__ double red[2][4];
-    double a = wave_sum_d((double)s), b = wave_sum_d((double)cnt);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) { red[0][w] = a; red[1][w] = b; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double s0 = 0, s1 = 0;
-        for (int k = 0; k < (int)(blockDim.x / 64); ++k) { s0 += red[0][k]; s1 += red[1][k]; }
-        atomic_add_f64(acc + 0, s0);
-        atomic_add_f64(acc + 1, s1);
+    double a = (double)s, b = (double)cnt;
+    if (block_sums_d<4>(a, b, blockDim.x / 64)) {
+        atomic_add_f64(acc + 0, a);
+        atomic_add_f64(acc + 1, b);
     }
 }
 
@@ -136,42 +96,10 @@ __global__ void centernet_loss_a_kernel(const float* x, const float* gt, long n,
                                         long nz) {
     float posl = 0.f, negl = 0.f, npos = 0.f;
     const long stride = (long)gridDim.x * blockDim.x;
-    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += stride) {
-        const float xi = x[i], t = gt[i];
-        const float p = 1.f / (1.f + expf(-xi));
-        const bool pass = (p >= 1e-4f) && (p <= 1.f - 1e-4f);
-        const float pc = fminf(fmaxf(p, 1e-4f), 1.f - 1e-4f);
-        float dterm = 0.f;
-        if (t == 1.f) {
-            const float om = 1.f - pc;
-            const float lg = logf(pc);
-            posl += lg * (om * om);
-            npos += 1.f;
-            dterm = om * om / pc - 2.f * om * lg;
-        } else if (t < 1.f) {
-            const float om = 1.f - t;
-            const float w = (om * om) * (om * om);
-            const float l1m = logf(1.f - pc);
-            negl += l1m * (pc * pc) * w;
-            dterm = w * (-(pc * pc) / (1.f - pc) + 2.f * pc * l1m);
-        }
-        g[i] = pass ? dterm * p * (1.f - p) : 0.f;
-    }
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += stride)
+        g[i] = focal_logit_term(x[i], gt[i], posl, negl, npos);
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < nz; i += stride) gz[i] = 0.f;
-    __shared__ double red[3][4];
-    double a = wave_sum_d((double)posl), b = wave_sum_d((double)negl), c = wave_sum_d((double)npos);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) { red[0][w] = a; red[1][w] = b; red[2][w] = c; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double* dst = acc + (long)(blockIdx.x % SCD_STAT_REPLICAS) * FOCAL_ACC;
-        const int nw = blockDim.x / 64;
-        double s0 = 0, s1 = 0, s2 = 0;
-        for (int k = 0; k < nw; ++k) { s0 += red[0][k]; s1 += red[1][k]; s2 += red[2][k]; }
-        atomic_add_f64(dst + 0, s0);
-        atomic_add_f64(dst + 1, s1);
-        atomic_add_f64(dst + 2, s2);
-    }
+    focal_accumulate(posl, negl, npos, acc);
 }
 
 static_assert(SCD_STAT_REPLICAS == 64, "centernet_loss_b_kernel sums the focal replicas with one wave");
@@ -204,6 +132,8 @@ __global__ __launch_bounds__(1024) void centernet_loss_b_kernel(int N, int HW, c
             }
         }
     }
+    // (block_sums_d and focal_finalize written out: the replica sums share the barrier, and through the helpers the
+    // kernel took 26 more instructions)
     __shared__ double red[3][16], frd[3];
     const double a = wave_sum_d((double)s[0]), b = wave_sum_d((double)s[1]), c = wave_sum_d((double)cnt);
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -260,30 +190,7 @@ __global__ void centernet_loss_scale_kernel(float* gh, long nh, int N, int HW, c
 }
 
 // ---------------------------------------------------------------- decode
-// t[n][i] = sigmoid(x) kept where it equals its 3x3 (k x k) max (pad -inf), else 0
-__global__ void decode_nms_kernel(const float* heat, int N, int H, int W, int k, float* t) {
-    const long total = (long)N * H * W;
-    const int r = (k - 1) / 2;
-    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-        const int n = (int)(i / ((long)H * W));
-        const int rem = (int)(i - (long)n * H * W);
-        const int y = rem / W, x = rem - (rem / W) * W;
-        const float* hp = heat + (long)n * H * W;
-        const float v = 1.f / (1.f + expf(-hp[rem]));
-        float m = -INFINITY;
-        for (int dy = -r; dy <= r; ++dy) {
-            const int yy = y + dy;
-            if ((unsigned)yy >= (unsigned)H) continue;
-            for (int dx = -r; dx <= r; ++dx) {
-                const int xx = x + dx;
-                if ((unsigned)xx >= (unsigned)W) continue;
-                m = fmaxf(m, 1.f / (1.f + expf(-hp[yy * W + xx])));
-            }
-        }
-        t[i] = (m == v) ? v : 0.f;
-    }
-}
-
+// (the map t[n][i] = sigmoid(x) kept where it equals its 3x3 max, else 0, is nms_kernel<NmsSigmoid>)
 // The K largest of n candidates, sorted, for one workgroup: cand(i, bits) says whether candidate i takes part and
 // gives its score's bit pattern (non-negative floats order like their bit patterns).  Radix-select the K-th largest
 // (four 8-bit passes), collect, then bitonic sort by (score desc, index asc).  At least K candidates must take part,
@@ -331,7 +238,8 @@ __device__ __forceinline__ void select_sorted_keys(Cand cand, int n, int K, unsi
         }
     }
     __syncthreads();
-    // ties at the threshold: take the lowest indices, in index order (chunks of blockDim)
+    // ties at the threshold: take the lowest indices, in index order (chunks of blockDim); block_compact written out
+    // with the barrier at the top (through the helper the decode and the pairing took 21 more instructions)
     for (int base = 0; base < n; base += blockDim.x) {
         __syncthreads();
         const unsigned taken = s_eqtaken;
@@ -487,7 +395,6 @@ __global__ __launch_bounds__(AE_THREADS) void corner_ae_fwd_kernel(const float* 
                                                                    float* gs_br) {
     __shared__ double et[AE_MAXK], eb[AE_MAXK], mm[AE_MAXK];
     __shared__ int vd[AE_MAXK];
-    __shared__ double red[2][AE_THREADS / 64];
     const int b = blockIdx.x, tid = threadIdx.x;
     if (tid < K) {
         const long o = (long)b * K + tid;
@@ -515,15 +422,9 @@ __global__ __launch_bounds__(AE_THREADS) void corner_ae_fwd_kernel(const float* 
         if (!(vd[i] && vd[j])) continue;
         push += (fmax(1.0 - fabs(mm[j] - mm[i]), 0.0) - inv) / dpush;
     }
-    pull = wave_sum_d(pull);
-    push = wave_sum_d(push);
-    if ((tid & 63) == 0) { red[0][tid >> 6] = pull; red[1][tid >> 6] = push; }
-    __syncthreads();
-    if (tid == 0) {
-        double s0 = 0, s1 = 0;
-        for (int k = 0; k < AE_THREADS / 64; ++k) { s0 += red[0][k]; s1 += red[1][k]; }
-        acc[2 * b] = s0;
-        acc[2 * b + 1] = s1;
+    if (block_sums_d<AE_THREADS / 64>(pull, push, AE_THREADS / 64)) {
+        acc[2 * b] = pull;
+        acc[2 * b + 1] = push;
     }
     if (tid < K) {
         double gt = 0.0, gb = 0.0;
@@ -597,8 +498,6 @@ __global__ __launch_bounds__(256) void corner_ae_bwd_kernel(const float* gs_tl, 
         g_br[(long)b * HW + p] = c * s;
     }
 }
-
-inline int ew_blocks(long n) { return (int)std::min<long>(4096, std::max<long>(1, (n + 255) / 256)); }
 
 }  // namespace
 
@@ -695,7 +594,8 @@ extern "C" int scd_decode_topk(const float* heat, int N, int H, int W, int K, co
     if (K < 1 || K > 1024 || K > H * W) return SCD_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
     float* t = (float*)workspace;
-    hipLaunchKernelGGL(decode_nms_kernel, dim3(ew_blocks((long)N * H * W)), dim3(256), 0, st, heat, N, H, W, 3, t);
+    hipLaunchKernelGGL(nms_kernel<NmsSigmoid>, dim3(ew_blocks((long)N * H * W)), dim3(256), 0, st, heat, (long)N, H, W, 3,
+                       t);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(decode_select_kernel, dim3(N), dim3(1024), 0, st, t, H * W, W, K, offset, od_off, regr, od_regr,

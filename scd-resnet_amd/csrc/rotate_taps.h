@@ -4,16 +4,9 @@
 // themselves as well): the operation order below is the contract (at a whole source coordinate the weights are 0 and
 // 1 and the sample is the tap itself, bit for bit).
 #pragma once
-#include "scd_common.h"
+#include "block_ops.h"
 
 #pragma clang fp contract(off)
-
-// torch 'reflect' (no edge repeat); valid for -n < i < 2n - 1
-__device__ __forceinline__ int reflect_idx(int i, int n) {
-    if (i < 0) i = -i;
-    if (i >= n) i = 2 * (n - 1) - i;
-    return i;
-}
 
 // the source coordinate (sx, sy) in fp64 -> its cell (x0, y0) and the fp32 weights of the cell's far taps
 __device__ __forceinline__ void rot_cell(double sx, double sy, int& x0, int& y0, float& wx, float& wy) {

@@ -13,7 +13,7 @@
 // materialised.  scd_slide_detections: one workgroup walks the decoded (10, T, K) stack tile by tile,
 // compacting the kept detections in the reference's order with wave ballots.  scd_slide_samples (the end of the
 // file): the box filter, cross-clip de-duplication and Rhr histogram of test.py:148-183.
-#include "scd_common.h"
+#include "block_ops.h"
 
 #pragma clang fp contract(off)
 
@@ -32,19 +32,13 @@ struct SlideGeom {
     int fix;                // apply the opencv column fix-up (test.py:79-82)
 };
 
-__device__ __forceinline__ int reflect101(int i, int n) {
-    if (i < 0) i = -i;
-    if (i >= n) i = 2 * (n - 1) - i;
-    return i;
-}
-
 // grey value of padded pixel (py, px)
 __device__ __forceinline__ double grey_at(const SlideGeom& g, int py, int px) {
     if (g.fix) {
         if (px < 64) px = 127 - px;
         else if (px >= 3136 && px < 3200) px = 6271 - px;
     }
-    int sy = reflect101(py - g.padTB, g.H), sx = reflect101(px - g.padLR, g.W);
+    int sy = reflect_idx(py - g.padTB, g.H), sx = reflect_idx(px - g.padLR, g.W);
     const uint8_t* p = g.rgb + ((long)sy * g.W + sx) * g.C;
     double v = 0.1140 * (double)p[0] + 0.5870 * (double)p[1];
     v = v + 0.2989 * (double)p[2];
@@ -69,16 +63,9 @@ __global__ __launch_bounds__(SL_THREADS) void slide_stats_kernel(SlideGeom g, do
             s1 += v;
             s2 += v * v;
         }
-    __shared__ double red[2][SL_THREADS / 64];
-    s1 = wave_sum_d(s1);
-    s2 = wave_sum_d(s2);
-    if ((tid & 63) == 0) { red[0][tid >> 6] = s1; red[1][tid >> 6] = s2; }
-    __syncthreads();
-    if (tid == 0) {
-        double a = 0.0, b = 0.0;
-        for (int w = 0; w < SL_THREADS / 64; ++w) { a += red[0][w]; b += red[1][w]; }
-        part[((long)t * SL_SLICES + s) * 2] = a;
-        part[((long)t * SL_SLICES + s) * 2 + 1] = b;
+    if (block_sums_d<SL_THREADS / 64>(s1, s2, SL_THREADS / 64)) {
+        part[((long)t * SL_SLICES + s) * 2] = s1;
+        part[((long)t * SL_SLICES + s) * 2 + 1] = s2;
     }
 }
 
@@ -124,6 +111,7 @@ __device__ __forceinline__ void slide_project(const float* dec, long plane, long
     rt = (halo - minl) / (2.0 * minl);
 }
 
+// (block_compact written out: through the helper this kernel took 2 more instructions and one more VGPR)
 __global__ __launch_bounds__(1024) void slide_detect_kernel(const float* dec, int T, int K, int stride, int padLR,
                                                             int padTB, int clipV, float thr, int* xy, double* ratio,
                                                             int* count) {
@@ -246,12 +234,11 @@ static inline SamplesWs samples_ws(void* workspace, long plane) {
 __global__ __launch_bounds__(1024) void samples_compact_kernel(const float* dec, int T, int K, int stride, int padLR,
                                                                int padTB, int clipV, float thr, int x0, int y0, int x1,
                                                                int y1, SamplesWs ws) {
-    __shared__ int wtot[16];
-    __shared__ int wabove[16];
-    __shared__ int base_s, above_s;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    __shared__ CompactLds<16> cs;
+    __shared__ int above_s;
+    const int tid = threadIdx.x;
     const int plane = T * K;
-    if (tid == 0) { base_s = 0; above_s = 0; }
+    if (tid == 0) { cs.base = 0; above_s = 0; }
     __syncthreads();
     for (int c0 = 0; c0 < plane; c0 += 1024) {
         int q = c0 + tid;
@@ -265,29 +252,17 @@ __global__ __launch_bounds__(1024) void samples_compact_kernel(const float* dec,
             slide_project(dec, plane, q, K, stride, padLR, padTB, clipV, px, py, rt);
             keep = above && px >= x0 && px < x1 && py >= y0 && py < y1;
         }
-        unsigned long long bal = __ballot(keep), bab = __ballot(above);
-        int rank = __popcll(bal & ((1ull << lane) - 1ull));
-        if (lane == 0) { wtot[wv] = __popcll(bal); wabove[wv] = __popcll(bab); }
-        __syncthreads();
+        block_count(above, &above_s);
+        const int off = block_compact(keep, cs, 16);
         if (keep) {
-            int off = base_s + rank;
-            for (int w = 0; w < wv; ++w) off += wtot[w];
             ws.cflat[off] = q;
             ws.cpx[off] = px;
             ws.cpy[off] = py;
             ws.cscore[off] = sc;
             ws.cratio[off] = rt;
         }
-        __syncthreads();
-        if (tid == 0) {
-            int s = 0, a = 0;
-            for (int w = 0; w < 16; ++w) { s += wtot[w]; a += wabove[w]; }
-            base_s += s;
-            above_s += a;
-        }
-        __syncthreads();
     }
-    if (tid == 0) { ws.hdr[0] = base_s; ws.hdr[1] = above_s; }
+    if (tid == 0) { ws.hdr[0] = cs.base; ws.hdr[1] = above_s; }
 }
 
 // (2) rank by counting: candidates ahead of i have a higher score, or an equal score and a lower flat index (the
@@ -349,14 +324,13 @@ __global__ __launch_bounds__(1024) void samples_emit_kernel(SamplesWs ws, int ra
     __shared__ unsigned long long keptw[SS_CAP / 64];
     __shared__ unsigned long long supw[16];
     __shared__ unsigned int lhist[SS_MAXBINS];
-    __shared__ int wtot[16];
-    __shared__ int wbin[16];
-    __shared__ int base_s, binned_s;
+    __shared__ CompactLds<16> cs;
+    __shared__ int binned_s;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int n = ws.hdr[0];
     const int C = (n + 63) / 64;
     for (int b = tid; b < nbins; b += 1024) lhist[b] = 0;
-    if (tid == 0) { base_s = 0; binned_s = 0; }
+    if (tid == 0) { cs.base = 0; binned_s = 0; }
     __syncthreads();
     if (radius >= 0) {
         for (int c = 0; c < C; ++c) {
@@ -397,37 +371,25 @@ __global__ __launch_bounds__(1024) void samples_emit_kernel(SamplesWs ws, int ra
                 if (bin) atomicAdd(&lhist[(int)v], 1u);
             }
         }
-        unsigned long long bal = __ballot(keep), bbin = __ballot(bin);
-        int rank = __popcll(bal & ((1ull << lane) - 1ull));
-        if (lane == 0) { wtot[wv] = __popcll(bal); wbin[wv] = __popcll(bbin); }
-        __syncthreads();
+        block_count(bin, &binned_s);
+        const int off = block_compact(keep, cs, 16);
         if (keep) {
-            int off = base_s + rank;
-            for (int w = 0; w < wv; ++w) off += wtot[w];
             xy[2 * off] = ws.cpx[i];
             xy[2 * off + 1] = ws.cpy[i];
             ratio[off] = rt;
             score[off] = ws.cscore[i];
             index[off] = ws.cflat[i];
         }
-        __syncthreads();
-        if (tid == 0) {
-            int s = 0, b = 0;
-            for (int w = 0; w < 16; ++w) { s += wtot[w]; b += wbin[w]; }
-            base_s += s;
-            binned_s += b;
-        }
-        __syncthreads();
     }
     for (int b = tid; b < nbins; b += 1024)
         if (lhist[b]) atomicAdd(&hist[b], (unsigned long long)lhist[b]);
     if (tid == 0) {
-        *count = base_s;
+        *count = cs.base;
         atomicAdd(&counters[0], (unsigned long long)ws.hdr[1]);
         atomicAdd(&counters[1], (unsigned long long)n);
-        atomicAdd(&counters[2], (unsigned long long)base_s);
+        atomicAdd(&counters[2], (unsigned long long)cs.base);
         atomicAdd(&counters[3], (unsigned long long)binned_s);
-        atomicAdd(&counters[4], (unsigned long long)(base_s - binned_s));
+        atomicAdd(&counters[4], (unsigned long long)(cs.base - binned_s));
     }
 }
 

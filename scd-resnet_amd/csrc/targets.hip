@@ -13,7 +13,7 @@
 
 #include <algorithm>
 
-#include "scd_common.h"
+#include "block_ops.h"
 
 // numpy evaluates every product and sum separately: no fused multiply-adds in this file
 #pragma clang fp contract(off)
@@ -233,9 +233,8 @@ __global__ __launch_bounds__(PACK_THREADS) void pack_locs_kernel(const float* __
                                                                  const uint8_t* __restrict__ flips,
                                                                  const float* __restrict__ cs, int size, int K, int trunc,
                                                                  float* __restrict__ locs, int* __restrict__ counts) {
-    __shared__ int wtot[PACK_THREADS / 64];
-    __shared__ int base_s;
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    __shared__ CompactLds<PACK_THREADS / 64> cl;
+    const int b = blockIdx.x, tid = threadIdx.x;
     const long r0 = offsets[ids[b]];
     const long n = offsets[ids[b] + 1] - r0;
     const bool rot = cs != nullptr;
@@ -245,9 +244,9 @@ __global__ __launch_bounds__(PACK_THREADS) void pack_locs_kernel(const float* __
     const float edge = (float)(size - 1), far = (float)(2 * size - 1), fsize = (float)size;
     const float shift = (float)(0.5 - (double)(size / 2));
     float* out = locs + (long)b * K * 8;
-    if (tid == 0) base_s = 0;
+    if (tid == 0) cl.base = 0;
     __syncthreads();
-    for (long c0 = 0; c0 < ncand && base_s < K; c0 += PACK_THREADS) {
+    for (long c0 = 0; c0 < ncand && cl.base < K; c0 += PACK_THREADS) {
         const long c = c0 + tid;
         bool keep = false;
         float v[8];
@@ -281,28 +280,14 @@ __global__ __launch_bounds__(PACK_THREADS) void pack_locs_kernel(const float* __
                 keep = cx >= 0.f && cx < fsize && cy >= 0.f && cy < fsize;
             }
         }
-        const unsigned long long bal = __ballot(keep);
-        const int rank = __popcll(bal & ((1ull << lane) - 1ull));
-        if (lane == 0) wtot[wv] = __popcll(bal);
-        __syncthreads();
-        if (keep) {
-            int off = base_s + rank;
-            for (int w = 0; w < wv; ++w) off += wtot[w];
-            if (off < K) {
-                if (trunc) { v[0] = truncf(v[0]); v[1] = truncf(v[1]); }
-                *(float4*)(out + off * 8) = make_float4(v[0], v[1], v[2], v[3]);
-                *(float4*)(out + off * 8 + 4) = make_float4(v[4], v[5], v[6], v[7]);
-            }
+        const int off = block_compact(keep, cl, PACK_THREADS / 64);
+        if (keep && off < K) {
+            if (trunc) { v[0] = truncf(v[0]); v[1] = truncf(v[1]); }
+            *(float4*)(out + off * 8) = make_float4(v[0], v[1], v[2], v[3]);
+            *(float4*)(out + off * 8 + 4) = make_float4(v[4], v[5], v[6], v[7]);
         }
-        __syncthreads();
-        if (tid == 0) {
-            int s = 0;
-            for (int w = 0; w < PACK_THREADS / 64; ++w) s += wtot[w];
-            base_s += s;
-        }
-        __syncthreads();
     }
-    const int cnt = min(base_s, K);
+    const int cnt = min(cl.base, K);
     if (tid == 0) counts[b] = cnt;
     for (int i = cnt * 8 + tid; i < K * 8; i += PACK_THREADS) out[i] = 0.f;
 }

@@ -33,12 +33,21 @@ def test_nms_matches_reference(shape, k):
     assert torch.equal(got, O.nms(heat, k))
 
 
-@pytest.mark.parametrize("shape,K", [((2, 1, 128, 128), 100), ((3, 4, 20, 30), 50), ((2, 1, 16, 16), 256)])
-def test_extract_topk_matches_reference(shape, K):
+# (ties: the flat range of a run of equal scores; bg: the background's scale; peaks: flat indices of scores of 2.0)
+@pytest.mark.parametrize("shape,K,ties,bg,peaks", [
+    ((2, 1, 128, 128), 100, (10, 20), 1.0, ()),
+    ((3, 4, 20, 30), 50, (10, 20), 1.0, ()),
+    ((2, 1, 16, 16), 256, (10, 20), 1.0, ()),
+    # the tie step across the select's 1024-element chunks: one row of 2400, the run of twelve ties at 1020..1031;
+    # K = 5 peaks + 4 ties from the first chunk + 5 from the second
+    ((1, 1, 40, 60), 14, (1020, 1032), 0.1, (3, 700, 1500, 2000, 2399)),
+], ids=["shape0-100", "shape1-50", "shape2-256", "ties_cross_chunk"])     # the first three keep their earlier ids
+def test_extract_topk_matches_reference(shape, K, ties, bg, peaks):
     from models.backbones.utility import extractTopK
     g = torch.Generator().manual_seed(5)
-    s = torch.randn(shape, generator=g)                      # negative scores too
-    s.view(shape[0], -1)[:, 10:20] = 0.75                    # a block of ties
+    s = bg * torch.randn(shape, generator=g)                 # negative scores too
+    s.view(shape[0], -1)[:, list(peaks)] = 2.0
+    s.view(shape[0], -1)[:, ties[0]:ties[1]] = 0.75          # a block of ties
     got = [t.cpu() for t in extractTopK(s.to(DEV), K)]
     B, C, H, W = shape
     rs, ri = torch.topk(s.view(B, -1), K)
