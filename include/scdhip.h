@@ -141,6 +141,16 @@ int scd_pack_weight(int dtype, const float* w, void* out, int A, int B, int T, i
  * of 64 (bf16) / 32 (fp32) channels.  C, Cp multiples of 8 (bf16) / 4 (fp32). */
 int scd_pad_channels(int dtype, const void* src, long rows, int C, int Cp, void* dst, void* stream);
 
+/* Hourglass up path (hourglass.py:113-114): nearest 2x upsample fused with the merge, NHWC.  up, out, dout are
+ * (N, 2h, 2w, C); low, dlow are (N, h, w, C).
+ *   scd_upsample2x_add      out[n][2i+a][2j+b][c] = up[n][2i+a][2j+b][c] + low[n][i][j][c], the sum in fp32, one rounding
+ *   scd_upsample2x_add_bwd  dlow[n][i][j][c] = (d00 + d01) + (d10 + d11) over dout's 2x2 block, fp32 in this order, one
+ *                           rounding; the gradient towards `up` is dout itself (no kernel)
+ * SCD_ERR_ARG: C not a multiple of 8 (16-bit types) / 4 (fp32), an extent <= 0, out == up or out == low (`up` is the
+ * ReLU mask its producing block keeps: the merge is never in place), dlow == dout. */
+int scd_upsample2x_add(int dtype, const void* up, const void* low, void* out, int N, int h, int w, int C, void* stream);
+int scd_upsample2x_add_bwd(int dtype, const void* dout, void* dlow, int N, int h, int w, int C, void* stream);
+
 /* Batched weight packing: all operand layouts of one training step in one launch.  descs (device memory)
  * are sorted by start; descriptor d covers elements [start, start + count) of the concatenated index space:
  * mode 0: out[row_off + a][t*B + b] = w[a][b][t], count = A * ldp (k >= T*B zero-filled);

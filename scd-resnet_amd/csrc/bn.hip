@@ -73,7 +73,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const T* y, T* out, int C
                                                        const float* rshift, int relu) {
     constexpr int E = Vec16<T>::N;
     constexpr int U = 4;
-    // the grid stride is a multiple of the chunks per row (C/E divides 256): a thread always owns the same
+    // the grid stride is a multiple of the chunks per row (ew_rows_ok, ew_grid): a thread always owns the same
     // E channels, so the per-channel parameters live in registers (no LDS, no bank conflicts).  U vectors
     // per thread are loaded before any is used (U x 16 B, x2 with a residual, in flight per thread).
     const unsigned cpr = (unsigned)C / E;
@@ -213,11 +213,12 @@ __global__ __launch_bounds__(256, BN_EW_WAVES) void bn_bwd_reduce_kernel(BwdRedu
     constexpr int E = Vec16<T>::N;
     constexpr int nt = 256;
     const int C = a.C, ld = a.ld;
-    const int cpr = C / E;                     // chunks per row of this channel slice (divides 256)
+    const int cpr = C / E;                     // chunks per row of this channel slice (<= 256)
     const int rpi = nt / cpr;                  // row lanes
     const int tid = threadIdx.x;
     const int ch = tid % cpr;
     const int rsub = tid / cpr;
+    const bool lane = rsub < rpi;              // false for the block's last 256 % cpr threads: no row lane, no rows
     const unsigned r0 = blockIdx.x * a.rows_per_block;
     const unsigned r1 = min(a.rows, r0 + a.rows_per_block);
     __shared__ float red[2 * nt * E];
@@ -266,14 +267,16 @@ __global__ __launch_bounds__(256, BN_EW_WAVES) void bn_bwd_reduce_kernel(BwdRedu
                 for (int e = 0; e < E; ++e) q[1][e] += d[e] * (yv[1][e] - mu[e]) * is[e];
             }
         };
-        loads_ahead_loop<BN_BWD_U, BwdRaw<NL>>(r0 + rsub, r1, rpi, load, acc);
+        loads_ahead_loop<BN_BWD_U, BwdRaw<NL>>(lane ? r0 + rsub : r1, r1, rpi, load, acc);
     });
     const int rep = (int)(blockIdx.x % SCD_STAT_REPLICAS);   // (mirrors stat_replica / stat_slot, gemm_common.h)
     // red[stat][rsub][channel].  Pass 1: sum dz (every layer's) and layer 0's sum dz*xhat; pass 2: layer 1's
+    if (lane) {
 #pragma unroll
-    for (int e = 0; e < E; ++e) {
-        red[rsub * C + ch * E + e] = s[e];
-        red[nt * E + rsub * C + ch * E + e] = q[0][e];
+        for (int e = 0; e < E; ++e) {
+            red[rsub * C + ch * E + e] = s[e];
+            red[nt * E + rsub * C + ch * E + e] = q[0][e];
+        }
     }
     __syncthreads();
     for (int c = tid; c < C; c += nt) {
@@ -288,8 +291,10 @@ __global__ __launch_bounds__(256, BN_EW_WAVES) void bn_bwd_reduce_kernel(BwdRedu
     }
     if constexpr (NL == 2) {
         __syncthreads();
+        if (lane) {
 #pragma unroll
-        for (int e = 0; e < E; ++e) red[nt * E + rsub * C + ch * E + e] = q[1][e];
+            for (int e = 0; e < E; ++e) red[nt * E + rsub * C + ch * E + e] = q[1][e];
+        }
         __syncthreads();
         for (int c = tid; c < C; c += nt) {
             double qq = 0.0;
@@ -368,10 +373,19 @@ __global__ __launch_bounds__(256, BN_EW_WAVES) void bn_bwd_apply_kernel(BwdApply
 }
 
 // elementwise BN kernels keep one channel chunk per thread: the grid stride (grid * 256 threads) must be a
-// multiple of the chunks per row cpr, i.e. cpr divides 256 or is a multiple of it (grid a multiple of cpr/256)
-inline bool ew_rows_ok(int cpr) { return cpr > 0 && (256 % cpr == 0 || cpr % 256 == 0); }
+// multiple of the chunks per row cpr.  Three kinds of row: cpr divides 256 (any grid), cpr is a multiple of 256 (grid a
+// multiple of cpr / 256), and rows of whole 128-byte lines below 256 chunks (cpr a multiple of 8: the hourglass's 192
+// channels are 24 bf16 / 48 fp32 chunks), whose grid is a multiple of cpr / gcd(cpr, 256) and whose reduction leaves
+// the last 256 % cpr threads of a block without a row lane.  Other widths (3 chunks, 12, ..) stay refused.
+inline bool ew_rows_ok(int cpr) {
+    return cpr > 0 && (256 % cpr == 0 || cpr % 256 == 0 || (cpr < 256 && cpr % 8 == 0));
+}
+inline long ew_grid_unit(int cpr) {
+    if (cpr > 256) return cpr / 256;
+    return cpr / (cpr & -cpr);                      // cpr <= 256: gcd(cpr, 256) is the largest power of two in cpr
+}
 inline int ew_grid(int resident, long nvec, int cpr) {
-    const long m = cpr > 256 ? cpr / 256 : 1;
+    const long m = ew_grid_unit(cpr);
     long g = std::min<long>(resident, (nvec + 255) / 256);
     g = std::max<long>(m, g / m * m);
     return (int)g;

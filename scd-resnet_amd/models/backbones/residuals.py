@@ -1,6 +1,6 @@
 """ResNet backbone + transposed-conv upsampler + terminal wiring, executed on libscdhip.
 
-Mirrors models/backbones/residuals.py of the reference (BasicBlock :84-120, Bottleneck
+Mirrors models/backbones/residuals.py of the reference (Residual :34-82, BasicBlock :84-120, Bottleneck
 :122-165, ResNetTerminal :167-182, ResNet :184-353, ResNetSpec :355-365): the same module
 tree is registered in the same order, so state_dict keys, parameter counts and the default
 initialisation (including the RNG draw order of ResNet.initialize) are identical.  The
@@ -17,6 +17,41 @@ from models.backbones.utility import convolution3x3
 from scdhip import blocks, ops
 
 BNMOMENTUM = 0.1
+
+
+class Residual(torch.nn.Module):
+    """The hourglass building block (residuals.py:34-82 of the reference): BasicBlock with the downsample named
+    ``skip`` -- an empty Sequential when the block keeps width and resolution.  Children are registered under the
+    reference's names in its order, so the state-dict keys are the reference's.  ``convSize`` and ``batchNorm`` are
+    placeholders there too."""
+
+    def __init__(self, convSize, inputDimension, outputDimension, stride=1, batchNorm=True):
+        super(Residual, self).__init__()
+        self.conv1 = torch.nn.Conv2d(inputDimension, outputDimension, (3, 3), padding=(1, 1), stride=(stride, stride),
+                                     bias=False)
+        self.bn1 = torch.nn.BatchNorm2d(outputDimension)
+        self.relu1 = torch.nn.ReLU(inplace=True)
+        self.conv2 = torch.nn.Conv2d(outputDimension, outputDimension, (3, 3), padding=(1, 1), bias=False)
+        self.bn2 = torch.nn.BatchNorm2d(outputDimension)
+        self.skip = torch.nn.Sequential(
+            torch.nn.Conv2d(inputDimension, outputDimension, (1, 1), stride=(stride, stride), bias=False),
+            torch.nn.BatchNorm2d(outputDimension)
+        ) if stride != 1 or inputDimension != outputDimension else torch.nn.Sequential()
+        self.relu = torch.nn.ReLU(inplace=True)
+
+    @property
+    def downsample(self):
+        """What blocks.ResidualFn reads: the (conv, bn) skip, or None for the identity.  A property, not a registered
+        child: ``skip`` stays the only name in the state dict."""
+        return self.skip if len(self.skip) else None
+
+    def forward(self, x):
+        """x: NHWC activation (compute dtype) -> NHWC activation."""
+        return blocks.ResidualFn.apply(x, self.conv1.weight, self)
+
+
+def residual3x3(dimension):
+    return Residual(3, dimension, dimension)
 
 
 class BasicBlock(torch.nn.Module):

@@ -1,18 +1,58 @@
 """Backbone utilities (models/backbones/utility.py of the reference).
 
-``convolution3x3`` builds the module used by BasicBlock.  The functional helpers keep the
+``convolution3x3`` builds the module used by BasicBlock; ``stackLayers`` .. ``changeDimensionConv`` are the
+hourglass's layer builders.  The functional helpers keep the
 reference API for user code and evaluation and run on libscdhip (scdhip.api: scd_nms, scd_topk);
 on the training/decode path the fused kernels take their place: gather + clampSigmoid inside
 scdhip.loss.CenterNetLossFn, NMS + top-K + gather inside scdhip.ops.decode_topk.
 """
 import torch
 
-from scdhip import api, ops
+from models.backbones.convolutions import Convolution
+from scdhip import api, blocks, ops
 
 
 def convolution3x3(inputDimension, outputDimension, stride=1):
     """utility.py:125-127"""
     return torch.nn.Conv2d(inputDimension, outputDimension, kernel_size=3, stride=stride, padding=1, bias=False)
+
+
+def stackLayers(convSize, inputDimension, outputDimension, modules, layer=Convolution, **kwargs):
+    """utility.py:35-39: `modules` layers, the width change in the first."""
+    layers = [layer(convSize, inputDimension, outputDimension, **kwargs)]
+    for _ in range(1, modules):
+        layers.append(layer(convSize, outputDimension, outputDimension, **kwargs))
+    return torch.nn.Sequential(*layers)
+
+
+def stackLayersReverted(k, inp_dim, out_dim, modules, layer=Convolution, **kwargs):
+    """utility.py:44-49: `modules` layers, the width change in the last."""
+    layers = [layer(k, inp_dim, inp_dim, **kwargs) for _ in range(modules - 1)]
+    layers.append(layer(k, inp_dim, out_dim, **kwargs))
+    return torch.nn.Sequential(*layers)
+
+
+class MergeUp(torch.nn.Module):
+    """utility.py:51-53, the hourglass merge ``up1 + up2``.  Here it is one pass with the nearest 2x upsample that
+    precedes it (blocks.UpsampleAddFn): the second argument is the low-resolution map *before* the upsample."""
+
+    def forward(self, element1, element2):
+        return blocks.UpsampleAddFn.apply(element1, element2)
+
+
+def mergeLayer(dim):
+    return MergeUp()
+
+
+def convolutionConv1x1(inputDimension, currentDimension, outputDimension):
+    """utility.py:61-65: the hourglass terminal, Conv3x3 + bias + ReLU then Conv1x1 (the shape blocks.HeadsFn fuses)."""
+    return torch.nn.Sequential(Convolution(3, inputDimension, currentDimension, batchNorm=False),
+                               torch.nn.Conv2d(currentDimension, outputDimension, (1, 1)))
+
+
+def changeDimensionConv(inputDimension, outputDimension):
+    """utility.py:67-68"""
+    return Convolution(3, inputDimension, outputDimension)
 
 
 def gatherFeatures(feature, indices, mask=None):

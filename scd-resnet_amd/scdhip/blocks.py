@@ -2,8 +2,10 @@
 
 Each Function runs one reference module group entirely on libscdhip kernels:
   StemFn        preprocess: Conv2d(1,64,7,s2,p3)+BN+ReLU+MaxPool(3,2,1)   residuals.py:209-216
-  ResidualFn    BasicBlock / Bottleneck (+downsample): one chain over the   residuals.py:84-165, 256-271
-                block's own conv1..conv3
+  StemConvFn    the hourglass stem: Convolution(7,1,C,s2), no pool         stackHourglass.py:130-134
+  ResidualFn    BasicBlock / Bottleneck / Residual (+downsample): one      residuals.py:34-165, 256-271
+                chain over the block's own conv1..conv3
+  UpsampleAddFn Upsample(2, nearest) + MergeUp of an hourglass level       hourglass.py:113-114
   DeconvBNFn    ConvTranspose2d(k4,s2,p1,no bias)+BN+ReLU                 residuals.py:286-310
   ConvBNFn      Convolution (conv+BN+ReLU) / conv+BN                      convolutions.py:25-49
   HeadsFn       all CenterNet terminals fused: one 3x3 GEMM with N = sum of
@@ -115,6 +117,52 @@ class StemFn(torch.autograd.Function):
             ops.conv_wgrad(dy, cols, 1, 1, 1, 0, ops.grad_of(conv.weight), (T, 1, 0), cvalid=T)
         grads_ready(conv, bn)
         return None, None, None, None, None
+
+
+class StemConvFn(torch.autograd.Function):
+    """The hourglass stem, Convolution(7, 1, C, stride=2) on the NCHW fp32 input (stackHourglass.py:130-134): StemFn
+    without the max-pool.  Any width but the direct kernel's 64 runs as im2col + a 1x1 GEMM (ops.stem_fwd)."""
+
+    @staticmethod
+    def forward(ctx, x, w, conv, bn, dtype):
+        training = bn.training
+        C = conv.weight.shape[0]
+        stats = ops.bn_stats(bn, "fwd") if training else None
+        wpk = ops.pack_weight(conv.weight, dtype, 0, ldp=64)
+        geom = tuple(conv.weight.shape) + (conv.stride[0], conv.padding[0])
+        y, cols, direct = ops.stem_fwd(x, wpk, geom, dtype, stats)
+        if direct:
+            raise NotImplementedError("StemConvFn keeps the im2col columns for its weight gradient; the 64-channel "
+                                      "direct stem belongs to StemFn")
+        st = ops.bn_finalize(bn, stats, C, y.numel() // C, training)
+        out = ops.bn_apply(y, st, True)
+        ctx.save_for_backward(cols, y)
+        ctx.st, ctx.conv, ctx.bn = st, conv, bn
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        conv, bn, st = ctx.conv, ctx.bn, ctx.st
+        cols, y = ctx.saved_tensors
+        dy = ops.bn_backward(bn, st, _c(dout), y, relu=True)
+        T = conv.weight.shape[2] * conv.weight.shape[3]
+        ops.conv_wgrad(dy, cols, 1, 1, 1, 0, ops.grad_of(conv.weight), (T, 1, 0), cvalid=T)
+        grads_ready(conv, bn)
+        return None, None, None, None, None
+
+
+class UpsampleAddFn(torch.autograd.Function):
+    """Upsample(scale_factor=2, nearest) + MergeUp of one hourglass level (hourglass.py:113-114): up + nearest_2x(low)
+    in one pass; backward hands dout itself to `up` and its 2x2 block sums to `low`."""
+
+    @staticmethod
+    def forward(ctx, up, low):
+        return ops.upsample_add(up, low)
+
+    @staticmethod
+    def backward(ctx, dout):
+        dout = _c(dout)
+        return dout, ops.upsample_add_bwd(dout)
 
 
 def _block_layers(blk):

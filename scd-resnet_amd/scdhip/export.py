@@ -21,9 +21,23 @@ _MODELS = {}        # (arch, mode, dtype, device) -> [Wrapper, key of the tensor
 _DTYPES = {"bf16": torch.bfloat16, "fp16": torch.float16, "fp32": torch.float32}
 
 
+def unsupported(arch, model):
+    """Why `arch` cannot go through the inference Wrapper (TorchScript export, slide.py), or None: the Wrapper and
+    its traced op cover the CenterNet ResNet family; the stacked hourglass trains and decodes through train.py only."""
+    from models.backbones.residuals import ResNet
+    if isinstance(model, ResNet):
+        return None
+    return ("architecture '%s' (%s) is not a CenterNet ResNet: TorchScript export, folded inference and slide "
+            "analysis are not built for it; it trains and validates through train.py" % (arch, type(model).__name__))
+
+
 def _plugin_model(arch):
     plugin = importlib.import_module("trainer.model." + arch)
-    return plugin.model(**plugin.modelParams)
+    model = plugin.model(**plugin.modelParams)
+    why = unsupported(arch, model)
+    if why:
+        raise NotImplementedError(why)
+    return model
 
 
 def _wrapper_for(arch, mode, dtype, device):

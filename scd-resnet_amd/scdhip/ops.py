@@ -1530,6 +1530,41 @@ def cpool_bwd(x, dy, direction):
     return dx
 
 
+def _upsample_shapes_ok(up, low):
+    return (up.dim() == 4 and low.dim() == 4 and up.dtype == low.dtype and up.is_contiguous() and low.is_contiguous()
+            and tuple(up.shape) == (low.shape[0], 2 * low.shape[1], 2 * low.shape[2], low.shape[3]))
+
+
+def upsample_add(up, low, out=None):
+    """The hourglass up path, out = up + nearest_2x(low) (scd_upsample2x_add; NHWC, up (N,2h,2w,C), low (N,h,w,C)).
+    Never in place: `up` is the ReLU mask its producing block keeps (the library refuses out == up / out == low)."""
+    if not _upsample_shapes_ok(up, low):
+        raise ValueError("upsample_add: up %s %s and low %s %s must be contiguous NHWC tensors of one dtype with up = "
+                         "(N, 2h, 2w, C) for low = (N, h, w, C)" % (tuple(up.shape), up.dtype, tuple(low.shape),
+                                                                    low.dtype))
+    _need_gpu(up, low, out)
+    N, h, w, C = low.shape
+    if out is None:
+        out = torch.empty_like(up)
+    elif out.shape != up.shape or out.dtype != up.dtype or not out.is_contiguous():
+        raise ValueError("upsample_add: out %s must be a contiguous tensor like up %s" % (tuple(out.shape),
+                                                                                          tuple(up.shape)))
+    L.call("scd_upsample2x_add", dt(up), ptr(up), ptr(low), ptr(out), N, h, w, C, stream())
+    return out
+
+
+def upsample_add_bwd(dout):
+    """Gradient of upsample_add towards `low`: the 2x2 block sums of dout (N,2h,2w,C) -> (N,h,w,C)
+    (scd_upsample2x_add_bwd).  The gradient towards `up` is dout itself."""
+    if dout.dim() != 4 or dout.shape[1] % 2 or dout.shape[2] % 2 or not dout.is_contiguous():
+        raise ValueError("upsample_add_bwd: dout %s must be a contiguous (N, 2h, 2w, C) tensor" % (tuple(dout.shape),))
+    _need_gpu(dout)
+    N, H, W, C = dout.shape
+    dlow = torch.empty(N, H // 2, W // 2, C, dtype=dout.dtype, device=dout.device)
+    L.call("scd_upsample2x_add_bwd", dt(dout), ptr(dout), ptr(dlow), N, H // 2, W // 2, C, stream())
+    return dlow
+
+
 def adam_step(p, g, m, v, lr, beta1, beta2, eps, step, gscale=1.0):
     bc1 = 1 - beta1 ** step
     bc2 = 1 - beta2 ** step

@@ -105,6 +105,10 @@ def load_wrapper(arch, ckpt, evalMode, foldMode):
     else:
         plugin = importlib.import_module("trainer.model." + arch)
         model = plugin.model(**plugin.modelParams)
+        from scdhip import export
+        why = export.unsupported(arch, model)
+        if why:
+            sys.exit("slide.py: " + why)
         model.load_state_dict(torch.load(ckpt, map_location="cpu", weights_only=True))
         model = model.cuda()
         model.train(not evalMode)

@@ -43,6 +43,10 @@ def begin(args):
     Logger.info("Loaded Model From: {}".format(modelPy))
     plugin = importlib.import_module(modelPy)
     model = plugin.model(**plugin.modelParams)
+    why = export.unsupported(args.modelArchitecture, model)
+    if why:
+        Logger.err(":: trace.py :: " + why)
+        sys.exit(1)
     if not os.path.exists(args.model):
         Logger.err(":: trace.py :: Pretrained Model Does not Exist: {}".format(args.model))
         sys.exit(1)
