@@ -72,3 +72,22 @@ template <typename I>
 __device__ __forceinline__ double* stat_slot(double* stats, I rep, int stat, int C, int c) {
     return stats + ((long)rep * 2 + stat) * C + c;
 }
+
+// The end of a 256-thread kernel whose thread t holds the sums s1 / s2 (stat 0 / 1) of the E channels of chunk
+// t % cpp (256 % cpp == 0, C = cpp * E): through red (LDS, [2][256][E + 1] floats, free by now) to one fp64 sum per
+// channel, threads in ascending order, added to the workgroup's replica
+template <int E>
+__device__ __forceinline__ void channel_sums_to_slots(const float* s1, const float* s2, float* red, int C, int cpp,
+                                                      double* stats) {
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int e = 0; e < E; ++e) { red[tid * (E + 1) + e] = s1[e]; red[(256 + tid) * (E + 1) + e] = s2[e]; }
+    __syncthreads();
+    for (int k = tid; k < 2 * C; k += 256) {
+        const int stat = k / C, c = k - (k / C) * C;
+        const int cc = c / E, e = c - (c / E) * E;
+        double a = 0.0;
+        for (int t = cc; t < 256; t += cpp) a += red[(stat * 256 + t) * (E + 1) + e];
+        atomic_add_f64(stat_slot(stats, stat_replica(blockIdx.x), stat, C, c), a);
+    }
+}

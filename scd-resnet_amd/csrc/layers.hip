@@ -1,6 +1,5 @@
-// Layer glue kernels: weight packing, stem im2col, stem BN+ReLU+MaxPool (fwd/bwd),
-// fused CenterNet head tails (1x1 convs), Adam.  All HBM-bound; 16-B vectorised where the
-// layout allows.
+// Layer glue kernels: weight packing, fused CenterNet head tails (1x1 convs) and their sparse backward, the
+// optimisers.  All HBM-bound; 16-B vectorised where the layout allows.  (The stem's kernels are in stem.hip.)
 #include <algorithm>
 
 #include "gemm_common.h"
@@ -174,331 +173,6 @@ __global__ __launch_bounds__(256) void pack_weights_batched_kernel(const scd_pac
         }
         if (bf16) ((h16*)q.out)[o] = (h16)v;
         else ((float*)q.out)[o] = v;
-    }
-}
-
-// ---------------------------------------------------------------- stem im2col
-template <typename T>
-__global__ void im2col_stem_kernel(const float* x, T* cols, int N, int H, int W, int Ho, int Wo, int kh, int kw,
-                                   int stride, int pad, int Kpad) {
-    constexpr int E = Vec16<T>::N;
-    const unsigned cpp = Kpad / E;
-    const unsigned total = (unsigned)N * Ho * Wo * cpp;
-    const unsigned HoWo = (unsigned)Ho * Wo;
-    for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
-        const unsigned pix = i / cpp;
-        const int ch = (int)(i - pix * cpp);
-        const int n = (int)(pix / HoWo);
-        const int rem = (int)(pix - (unsigned)n * HoWo);
-        const int oh = rem / Wo, ow = rem - (rem / Wo) * Wo;
-        float v[E];
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-            const int k = ch * E + e;
-            float val = 0.f;
-            if (k < kh * kw) {
-                const int r = k / kw, s = k - (k / kw) * kw;
-                const int ih = oh * stride - pad + r, iw = ow * stride - pad + s;
-                if ((unsigned)ih < (unsigned)H && (unsigned)iw < (unsigned)W) val = x[((long)n * H + ih) * W + iw];
-            }
-            v[e] = val;
-        }
-        Vec16<T>::store(cols + (size_t)pix * Kpad + ch * E, v);
-    }
-}
-
-// ---------------------------------------------------------------- stem BN+ReLU+MaxPool(3,2,1)
-// One thread = one 16-B channel chunk of SPR consecutive pooled rows at one pooled column: it loads the 2 SPR + 1 conv
-// rows x 3 conv columns of those windows at once (clamped addresses; taps outside the image never win).  Conv row
-// 2 oh + 1 is the bottom of window oh and the top of window oh + 1, so one row per thread fetches 1.5x the conv output
-// (PMC, round 4) and four rows per thread 9/8 -- but in the step the conv output was just written and is read back
-// from the Infinity Cache, and the four-row build (203 VGPRs, 2 waves per SIMD) measured 99 us against 82 us for one
-// row per thread (round 5, tools/gpu_abn.sh): one row per thread stays.
-// workgroups of 256 per CU the pool is compiled for (registers: the window loads in flight per thread)
-#ifndef STEM_POOL_OCC
-#define STEM_POOL_OCC 4
-#endif
-#ifndef STEM_SPR
-#define STEM_SPR 1
-#endif
-constexpr int SPR = STEM_SPR;                       // pooled rows per thread
-template <typename T>
-__global__ __launch_bounds__(256, STEM_POOL_OCC) void stem_pool_fwd_kernel(const T* y, const float* scale, const float* shift, T* out, uint8_t* argmax,
-                                     int N, int H, int W, int C, int Ho, int Wo) {
-    constexpr int E = Vec16<T>::N;
-    constexpr int NR = 2 * SPR + 1;
-    const unsigned cpp = C / E;
-    const unsigned G = (unsigned)(Ho + SPR - 1) / SPR;
-    const unsigned GW = G * (unsigned)Wo;
-    const unsigned total = (unsigned)N * GW * cpp;
-    for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
-        const unsigned item = i / cpp;
-        const int ch = (int)(i - item * cpp);
-        const int n = (int)(item / GW);
-        const unsigned rem = item - (unsigned)n * GW;
-        const int g = (int)(rem / (unsigned)Wo), ow = (int)(rem - (unsigned)g * Wo);
-        const int oh0 = g * SPR;
-        float sc[E], sh[E];
-#pragma unroll
-        for (int e = 0; e < E; ++e) { sc[e] = scale[ch * E + e]; sh[e] = shift[ch * E + e]; }
-        uint4 raw[NR][3];
-#pragma unroll
-        for (int r = 0; r < NR; ++r)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const int h = min(max(2 * oh0 - 1 + r, 0), H - 1), w = min(max(2 * ow - 1 + c, 0), W - 1);
-                raw[r][c] = *(const uint4*)(y + (((long)n * H + h) * W + w) * C + ch * E);
-            }
-#pragma unroll
-        for (int j = 0; j < SPR; ++j) {
-            const int oh = oh0 + j;
-            float best[E];
-            int arg[E];
-#pragma unroll
-            for (int e = 0; e < E; ++e) { best[e] = -INFINITY; arg[e] = 0; }
-            // the window in window order (first maximum wins, as before)
-#pragma unroll
-            for (int d = 0; d < 9; ++d) {
-                const bool in = (unsigned)(2 * oh - 1 + d / 3) < (unsigned)H && (unsigned)(2 * ow - 1 + d % 3) < (unsigned)W;
-                float v[E];
-                Vec16<T>::load(&raw[2 * j + d / 3][d % 3], v);
-#pragma unroll
-                for (int e = 0; e < E; ++e) {
-                    const float z = in ? fmaxf(v[e] * sc[e] + sh[e], 0.f) : -INFINITY;
-                    if (z > best[e]) { best[e] = z; arg[e] = d; }
-                }
-            }
-            if (oh < Ho) {
-                const size_t pix = ((size_t)n * Ho + oh) * Wo + ow;
-                Vec16<T>::store(out + pix * C + ch * E, best);
-                // the E argmax bytes of this chunk in one store
-                unsigned lo = 0, hi = 0;
-#pragma unroll
-                for (int e = 0; e < E && e < 4; ++e) lo |= (unsigned)arg[e] << (8 * e);
-#pragma unroll
-                for (int e = 4; e < E; ++e) hi |= (unsigned)arg[e] << (8 * (e - 4));
-                if constexpr (E == 8) *(uint2*)(argmax + pix * C + ch * E) = make_uint2(lo, hi);
-                else *(unsigned*)(argmax + pix * C + ch * E) = lo;
-            }
-        }
-    }
-}
-
-template <typename T>
-__global__ void stem_pool_bwd_kernel(const T* dout, const uint8_t* argmax, const T* y, const float* scale,
-                                     const float* shift, T* dz, int N, int H, int W, int C, int Ho, int Wo) {
-    constexpr int E = Vec16<T>::N;
-    const unsigned cpp = C / E;
-    const unsigned total = (unsigned)N * H * W * cpp;
-    const unsigned HW = (unsigned)H * W;
-    for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
-        const size_t pix = i / cpp;
-        const int ch = (int)(i - (unsigned)pix * cpp);
-        const int n = (int)((unsigned)pix / HW);
-        const int rem = (int)((unsigned)pix - (unsigned)n * HW);
-        const int h = rem / W, w = rem - (rem / W) * W;
-        float acc[E];
-#pragma unroll
-        for (int e = 0; e < E; ++e) acc[e] = 0.f;
-        const int oh0 = h / 2, oh1 = min(Ho - 1, (h + 1) / 2);
-        const int ow0 = w / 2, ow1 = min(Wo - 1, (w + 1) / 2);
-        for (int oh = oh0; oh <= oh1; ++oh) {
-            const int di = h - (2 * oh - 1);
-            if (di < 0 || di > 2) continue;
-            for (int ow = ow0; ow <= ow1; ++ow) {
-                const int dj = w - (2 * ow - 1);
-                if (dj < 0 || dj > 2) continue;
-                const long o = (((long)n * Ho + oh) * Wo + ow) * C + ch * E;
-                float d[E];
-                Vec16<T>::load(dout + o, d);
-#pragma unroll
-                for (int e = 0; e < E; ++e)
-                    if (argmax[o + e] == di * 3 + dj) acc[e] += d[e];
-            }
-        }
-        float v[E];
-        Vec16<T>::load(y + pix * C + ch * E, v);
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-            const float z = v[e] * scale[ch * E + e] + shift[ch * E + e];
-            acc[e] = z > 0.f ? acc[e] : 0.f;
-        }
-        Vec16<T>::store(dz + pix * C + ch * E, acc);
-    }
-}
-
-// Stem MaxPool backward + ReLU mask (as stem_pool_bwd_kernel) fused with the stem BN backward reduction:
-// the same pass accumulates sum dz and sum dz*(y-mean)*invstd per channel (fp64 replica slots), so the
-// separate reduce pass over dz and y is gone.  The grid stride is a multiple of the chunks per pixel, so a
-// thread always owns the same 8 (bf16) channels.
-template <typename T>
-__global__ __launch_bounds__(256) void stem_pool_bwd_bn_kernel(const T* dout, const uint8_t* argmax, const T* y,
-                                                               const float* scale, const float* shift, const float* mean,
-                                                               const float* invstd, T* dz, double* stats, int N, int H,
-                                                               int W, int C, int Ho, int Wo) {
-    constexpr int E = Vec16<T>::N;
-    const unsigned cpp = C / E;
-    const unsigned total = (unsigned)N * H * W * cpp;
-    const unsigned HW = (unsigned)H * W;
-    const int ch = (int)(threadIdx.x % cpp);
-    float sc[E], sh[E], mu[E], is[E], s1[E], s2[E];
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-        sc[e] = scale[ch * E + e]; sh[e] = shift[ch * E + e]; mu[e] = mean[ch * E + e]; is[e] = invstd[ch * E + e];
-        s1[e] = 0.f; s2[e] = 0.f;
-    }
-    for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
-        const size_t pix = i / cpp;
-        const int n = (int)((unsigned)pix / HW);
-        const int rem = (int)((unsigned)pix - (unsigned)n * HW);
-        const int h = rem / W, w = rem - (rem / W) * W;
-        float acc[E];
-#pragma unroll
-        for (int e = 0; e < E; ++e) acc[e] = 0.f;
-        const int oh0 = h / 2, oh1 = min(Ho - 1, (h + 1) / 2);
-        const int ow0 = w / 2, ow1 = min(Wo - 1, (w + 1) / 2);
-        for (int oh = oh0; oh <= oh1; ++oh) {
-            const int di = h - (2 * oh - 1);
-            if (di < 0 || di > 2) continue;
-            for (int ow = ow0; ow <= ow1; ++ow) {
-                const int dj = w - (2 * ow - 1);
-                if (dj < 0 || dj > 2) continue;
-                const long o = (((long)n * Ho + oh) * Wo + ow) * C + ch * E;
-                float d[E];
-                Vec16<T>::load(dout + o, d);
-                uint8_t am[E];
-                if constexpr (E == 8) *(uint2*)am = *(const uint2*)(argmax + o);
-                else *(uint32_t*)am = *(const uint32_t*)(argmax + o);
-                const int sel = di * 3 + dj;
-#pragma unroll
-                for (int e = 0; e < E; ++e)
-                    if (am[e] == sel) acc[e] += d[e];
-            }
-        }
-        float v[E];
-        Vec16<T>::load(y + pix * C + ch * E, v);
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-            const float z = v[e] * sc[e] + sh[e];
-            acc[e] = z > 0.f ? acc[e] : 0.f;
-        }
-        Vec16<T>::store(dz + pix * C + ch * E, acc);
-        // BN backward sums of the value the apply pass will see (the stored, rounded dz)
-        float r[E];
-#pragma unroll
-        for (int e = 0; e < E; ++e) r[e] = to_f<T>(from_f<T>(acc[e]));
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-            s1[e] += r[e];
-            s2[e] += r[e] * (v[e] - mu[e]) * is[e];
-        }
-    }
-    __shared__ float red[2][256][E + 1];
-#pragma unroll
-    for (int e = 0; e < E; ++e) { red[0][threadIdx.x][e] = s1[e]; red[1][threadIdx.x][e] = s2[e]; }
-    __syncthreads();
-    // channel c = ch*E + e is held by threads t with t % cpp == ch
-    for (int k = threadIdx.x; k < 2 * C; k += blockDim.x) {
-        const int stat = k / C, c = k - (k / C) * C;
-        const int cc = c / E, e = c - (c / E) * E;
-        double a = 0.0;
-        for (int t = cc; t < (int)blockDim.x; t += cpp) a += red[stat][t][e];
-        atomic_add_f64(stat_slot(stats, stat_replica(blockIdx.x), stat, C, c), a);
-    }
-}
-
-// The same pass for even inputs (H = 2 Ho, W = 2 Wo), one thread per 2x2 input block and 16-B channel chunk:
-// input rows {2oh, 2oh+1} x cols {2ow, 2ow+1} are covered only by pooled outputs (oh..oh+1, ow..ow+1), so the
-// thread issues its 4 gradient vectors, 4 argmax words and 4 activation vectors together (no data-dependent
-// branches around loads) and each pooled gradient is read ~once per 4 inputs.  Window position of input
-// (2oh+a, 2ow+b) in output (oh+i, ow+j): di = a - 2i + 1, dj = b - 2j + 1; sums run over outputs in
-// (oh, ow) order as the generic kernel's loops do.
-template <typename T>
-__global__ __launch_bounds__(256) void stem_pool_bwd_bn_2x2_kernel(const T* dout, const uint8_t* argmax, const T* y,
-                                                                   const float* scale, const float* shift,
-                                                                   const float* mean, const float* invstd, T* dz,
-                                                                   double* stats, int N, int C, int Ho, int Wo) {
-    constexpr int E = Vec16<T>::N;
-    const unsigned cpp = C / E;
-    const unsigned total = (unsigned)N * Ho * Wo * cpp;
-    const unsigned HWo = (unsigned)Ho * Wo;
-    const int W = 2 * Wo;
-    const int ch = (int)(threadIdx.x % cpp);
-    float sc[E], sh[E], mu[E], is[E], s1[E], s2[E];
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-        sc[e] = scale[ch * E + e]; sh[e] = shift[ch * E + e]; mu[e] = mean[ch * E + e]; is[e] = invstd[ch * E + e];
-        s1[e] = 0.f; s2[e] = 0.f;
-    }
-    for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
-        const unsigned blk = i / cpp;
-        const unsigned n = blk / HWo;
-        const unsigned rem = blk - n * HWo;
-        const int oh = (int)(rem / Wo), ow = (int)(rem - (rem / Wo) * Wo);
-        const bool okh = oh + 1 < Ho, okw = ow + 1 < Wo;
-        // pooled outputs O[i][j] = (oh+i, ow+j); out-of-range ones read O[0][0] and are ignored
-        float d[2][2][E];
-        uint8_t am[2][2][E];
-        float v[2][2][E];
-#pragma unroll
-        for (int oi = 0; oi < 2; ++oi)
-#pragma unroll
-            for (int oj = 0; oj < 2; ++oj) {
-                const bool ok = (oi == 0 || okh) && (oj == 0 || okw);
-                const unsigned o = ((n * Ho + oh + (ok ? oi : 0)) * Wo + ow + (ok ? oj : 0)) * C + ch * E;
-                Vec16<T>::load(dout + o, d[oi][oj]);
-                if constexpr (E == 8) *(uint2*)am[oi][oj] = *(const uint2*)(argmax + o);
-                else *(uint32_t*)am[oi][oj] = *(const uint32_t*)(argmax + o);
-                if (!ok)
-#pragma unroll
-                    for (int e = 0; e < E; ++e) am[oi][oj][e] = 0xff;
-            }
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int b = 0; b < 2; ++b)
-                Vec16<T>::load(y + ((n * (2 * Ho) + 2 * oh + a) * W + 2 * ow + b) * (unsigned)C + ch * E, v[a][b]);
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int b = 0; b < 2; ++b) {
-                float acc[E];
-#pragma unroll
-                for (int e = 0; e < E; ++e) acc[e] = 0.f;
-#pragma unroll
-                for (int oi = 0; oi < 2; ++oi)
-#pragma unroll
-                    for (int oj = 0; oj < 2; ++oj) {
-                        if (oi > a || oj > b) continue;                // (a=0 -> only i=0; a=1 -> i=0,1)
-                        const int sel = (a - 2 * oi + 1) * 3 + (b - 2 * oj + 1);
-#pragma unroll
-                        for (int e = 0; e < E; ++e)
-                            if (am[oi][oj][e] == sel) acc[e] += d[oi][oj][e];
-                    }
-#pragma unroll
-                for (int e = 0; e < E; ++e) {
-                    const float z = v[a][b][e] * sc[e] + sh[e];
-                    acc[e] = z > 0.f ? acc[e] : 0.f;
-                }
-                Vec16<T>::store(dz + ((n * (2 * Ho) + 2 * oh + a) * W + 2 * ow + b) * (unsigned)C + ch * E, acc);
-#pragma unroll
-                for (int e = 0; e < E; ++e) {
-                    const float r = to_f<T>(from_f<T>(acc[e]));
-                    s1[e] += r;
-                    s2[e] += r * (v[a][b][e] - mu[e]) * is[e];
-                }
-            }
-    }
-    __shared__ float red[2][256][E + 1];
-#pragma unroll
-    for (int e = 0; e < E; ++e) { red[0][threadIdx.x][e] = s1[e]; red[1][threadIdx.x][e] = s2[e]; }
-    __syncthreads();
-    for (int k = threadIdx.x; k < 2 * C; k += blockDim.x) {
-        const int stat = k / C, c = k - (k / C) * C;
-        const int cc = c / E, e = c - (c / E) * E;
-        double a = 0.0;
-        for (int t = cc; t < (int)blockDim.x; t += cpp) a += red[stat][t][e];
-        atomic_add_f64(stat_slot(stats, stat_replica(blockIdx.x), stat, C, c), a);
     }
 }
 
@@ -723,75 +397,6 @@ extern "C" int scd_pack_weight(int dtype, const float* w, void* out, int A, int 
     });
 }
 
-extern "C" int scd_im2col_stem(int dtype, const float* x, void* cols, int N, int H, int W, int Ho, int Wo, int kh,
-                               int kw, int stride, int pad, int Kpad, void* stream) {
-    SCD_F16_FWD(scd_im2col_stem, x, cols, N, H, W, Ho, Wo, kh, kw, stride, pad, Kpad, stream);
-    if (Kpad % 8 || Kpad < kh * kw) return SCD_ERR_ARG;
-    return scd_dispatch_dtype(dtype, [&](auto tag) {
-        using T = typename decltype(tag)::type;
-        constexpr int E = 16 / sizeof(T);
-        const long total = (long)N * Ho * Wo * (Kpad / E);
-        hipLaunchKernelGGL((im2col_stem_kernel<T>), dim3(ew_blocks(total)), dim3(256), 0, (hipStream_t)stream, x,
-                           (T*)cols, N, H, W, Ho, Wo, kh, kw, stride, pad, Kpad);
-        SCD_RETURN_LAUNCH();
-    });
-}
-
-extern "C" int scd_stem_pool_fwd(int dtype, const void* y, const float* scale, const float* shift, void* out,
-                                 uint8_t* argmax, int N, int H, int W, int C, int Ho, int Wo, void* stream) {
-    SCD_F16_FWD(scd_stem_pool_fwd, y, scale, shift, out, argmax, N, H, W, C, Ho, Wo, stream);
-    return scd_dispatch_dtype(dtype, [&](auto tag) {
-        using T = typename decltype(tag)::type;
-        constexpr int E = 16 / sizeof(T);
-        if (C % E) return SCD_ERR_ARG;
-        const long total = (long)N * ((Ho + SPR - 1) / SPR) * Wo * (C / E);
-        if (total >= (1L << 32)) return SCD_ERR_ARG;
-        hipLaunchKernelGGL((stem_pool_fwd_kernel<T>), dim3(ew_blocks(total)), dim3(256), 0, (hipStream_t)stream,
-                           (const T*)y, scale, shift, (T*)out, argmax, N, H, W, C, Ho, Wo);
-        SCD_RETURN_LAUNCH();
-    });
-}
-
-extern "C" int scd_stem_pool_bwd(int dtype, const void* dout, const uint8_t* argmax, const void* y, const float* scale,
-                                 const float* shift, void* dz, int N, int H, int W, int C, int Ho, int Wo, void* stream) {
-    SCD_F16_FWD(scd_stem_pool_bwd, dout, argmax, y, scale, shift, dz, N, H, W, C, Ho, Wo, stream);
-    return scd_dispatch_dtype(dtype, [&](auto tag) {
-        using T = typename decltype(tag)::type;
-        constexpr int E = 16 / sizeof(T);
-        if (C % E) return SCD_ERR_ARG;
-        const long total = (long)N * H * W * (C / E);
-        hipLaunchKernelGGL((stem_pool_bwd_kernel<T>), dim3(ew_blocks(total)), dim3(256), 0, (hipStream_t)stream,
-                           (const T*)dout, argmax, (const T*)y, scale, shift, (T*)dz, N, H, W, C, Ho, Wo);
-        SCD_RETURN_LAUNCH();
-    });
-}
-
-extern "C" int scd_stem_pool_bwd_bn(int dtype, const void* dout, const uint8_t* argmax, const void* y, const float* scale,
-                                    const float* shift, const float* mean, const float* invstd, void* dz, double* stats,
-                                    int N, int H, int W, int C, int Ho, int Wo, void* stream) {
-    SCD_F16_FWD(scd_stem_pool_bwd_bn, dout, argmax, y, scale, shift, mean, invstd, dz, stats, N, H, W, C, Ho, Wo, stream);
-    return scd_dispatch_dtype(dtype, [&](auto tag) {
-        using T = typename decltype(tag)::type;
-        constexpr int E = 16 / sizeof(T);
-        hipStream_t st = (hipStream_t)stream;
-        if (C % E || 256 % (C / E)) return SCD_ERR_ARG;
-        const long total = (long)N * H * W * (C / E);
-        if (H == 2 * Ho && W == 2 * Wo && (long)N * H * W * C < (1L << 31)) {
-            static const int g2 = resident_grid((const void*)stem_pool_bwd_bn_2x2_kernel<T>, 256);
-            const long blocks2 = (long)N * Ho * Wo * (C / E);
-            const int grid = (int)std::min<long>(g2, (blocks2 + 255) / 256);
-            hipLaunchKernelGGL((stem_pool_bwd_bn_2x2_kernel<T>), dim3(grid), dim3(256), 0, st, (const T*)dout, argmax,
-                               (const T*)y, scale, shift, mean, invstd, (T*)dz, stats, N, C, Ho, Wo);
-            SCD_RETURN_LAUNCH();
-        }
-        static const int g = resident_grid((const void*)stem_pool_bwd_bn_kernel<T>, 256);
-        const int blocks = (int)std::min<long>(g, (total + 255) / 256);
-        hipLaunchKernelGGL((stem_pool_bwd_bn_kernel<T>), dim3(blocks), dim3(256), 0, st, (const T*)dout, argmax,
-                           (const T*)y, scale, shift, mean, invstd, (T*)dz, stats, N, H, W, C, Ho, Wo);
-        SCD_RETURN_LAUNCH();
-    });
-}
-
 extern "C" int scd_heads_fwd(int dtype, const void* hid, int N, int HW, int nh, int Hd, const int* od,
                              const float* const* w1, const float* const* b1, float* const* outs, void* stream) {
     SCD_F16_FWD(scd_heads_fwd, hid, N, HW, nh, Hd, od, w1, b1, outs, stream);
@@ -811,29 +416,48 @@ extern "C" int scd_heads_fwd(int dtype, const void* hid, int N, int HW, int nh, 
     });
 }
 
-extern "C" int scd_heads_bwd(int dtype, const void* hid, int N, int HW, int nh, int Hd, const int* od,
-                             const float* const* w1, const float* const* douts, void* dhid, double* acc,
-                             void* stream) {
-    SCD_F16_FWD(scd_heads_bwd, hid, N, HW, nh, Hd, od, w1, douts, dhid, acc, stream);
+// The tail backward launch over heads [0, nd).  PK = false (scd_heads_bwd): the kernel reads the NCHW head-output
+// gradients; PK = true (scd_heads_bwd_packed_split): heads_pack_kernel first writes them, times dscale, pixel-major
+// into `packed`, and the kernel reads those
+template <bool PK>
+static int launch_heads_bwd(int dtype, const void* hid, int N, int HW, int nh, int Hd, const int* od, int nd,
+                            const float* const* w1, const float* const* douts, float dscale, float* packed, void* dhid,
+                            double* acc, void* stream) {
     HeadsDesc d;
-    if (!make_desc(d, nh, Hd, od)) return SCD_ERR_ARG;
+    if (!make_desc(d, nh, Hd, od) || (PK && !packed) || nd < 1 || nd > nh) return SCD_ERR_ARG;
+    d.nd = nd;
+    d.dstride = nd * Hd;
     return scd_dispatch_dtype(dtype, [&](auto tag) {
         using T = typename decltype(tag)::type;
         constexpr int E = 16 / sizeof(T);
-        const int cpp = nh * Hd / E;
+        const int cpp = nd * Hd / E;
         if (cpp > 256 || (Hd % E)) return SCD_ERR_ARG;
         for (int h = 0; h < nh; ++h) { d.w1[h] = w1[h]; d.dout[h] = douts[h]; }
         const int accsz = d.nout * Hd + d.nout + nh * Hd;
         const long P = (long)N * HW;
         if (P * nh * Hd >= (1L << 31)) return SCD_ERR_ARG;     // 32-bit element offsets
+        hipStream_t st = (hipStream_t)stream;
+        if constexpr (PK) {
+            hipLaunchKernelGGL(heads_pack_kernel, dim3(ew_blocks(P)), dim3(256), 0, st, N, HW, d, dscale, packed);
+            hipError_t e = hipGetLastError();
+            if (e != hipSuccess) return (int)e;
+            d.pk = packed;
+        }
         const int G = 512 / cpp;                                // pixel lanes (cpp <= 256 -> G >= 2)
         const int threads = G * cpp;
         const int PXB = 2048;                              // one 1-per-CU round at B=32, 128x128
         const int blocks = cdiv(P, PXB);
-        hipLaunchKernelGGL((heads_bwd_kernel<T, E>), dim3(blocks), dim3(threads), 0, (hipStream_t)stream,
-                           (const T*)hid, N, HW, d, (T*)dhid, acc, accsz, PXB);
+        hipLaunchKernelGGL((heads_bwd_kernel<T, E, PK>), dim3(blocks), dim3(threads), 0, st, (const T*)hid, N, HW, d,
+                           (T*)dhid, acc, accsz, PXB);
         SCD_RETURN_LAUNCH();
     });
+}
+
+extern "C" int scd_heads_bwd(int dtype, const void* hid, int N, int HW, int nh, int Hd, const int* od,
+                             const float* const* w1, const float* const* douts, void* dhid, double* acc,
+                             void* stream) {
+    SCD_F16_FWD(scd_heads_bwd, hid, N, HW, nh, Hd, od, w1, douts, dhid, acc, stream);
+    return launch_heads_bwd<false>(dtype, hid, N, HW, nh, Hd, od, nh, w1, douts, 1.f, nullptr, dhid, acc, stream);
 }
 
 extern "C" int scd_heads_bwd_packed(int dtype, const void* hid, int N, int HW, int nh, int Hd, const int* od,
@@ -847,32 +471,7 @@ extern "C" int scd_heads_bwd_packed_split(int dtype, const void* hid, int N, int
                                           int nd, const float* const* w1, const float* const* douts, float dscale,
                                           float* packed, void* dhid, double* acc, void* stream) {
     SCD_F16_FWD(scd_heads_bwd_packed_split, hid, N, HW, nh, Hd, od, nd, w1, douts, dscale, packed, dhid, acc, stream);
-    HeadsDesc d;
-    if (!make_desc(d, nh, Hd, od) || !packed || nd < 1 || nd > nh) return SCD_ERR_ARG;
-    d.nd = nd;
-    d.dstride = nd * Hd;
-    return scd_dispatch_dtype(dtype, [&](auto tag) {
-        using T = typename decltype(tag)::type;
-        constexpr int E = 16 / sizeof(T);
-        const int cpp = nd * Hd / E;
-        if (cpp > 256 || (Hd % E)) return SCD_ERR_ARG;
-        for (int h = 0; h < nh; ++h) { d.w1[h] = w1[h]; d.dout[h] = douts[h]; }
-        const int accsz = d.nout * Hd + d.nout + nh * Hd;
-        const long P = (long)N * HW;
-        if (P * nh * Hd >= (1L << 31)) return SCD_ERR_ARG;
-        hipStream_t st = (hipStream_t)stream;
-        hipLaunchKernelGGL(heads_pack_kernel, dim3(ew_blocks(P)), dim3(256), 0, st, N, HW, d, dscale, packed);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return (int)e;
-        d.pk = packed;
-        const int G = 512 / cpp;
-        const int threads = G * cpp;
-        const int PXB = 2048;
-        const int blocks = cdiv(P, PXB);
-        hipLaunchKernelGGL((heads_bwd_kernel<T, E, true>), dim3(blocks), dim3(threads), 0, st, (const T*)hid, N, HW,
-                           d, (T*)dhid, acc, accsz, PXB);
-        SCD_RETURN_LAUNCH();
-    });
+    return launch_heads_bwd<true>(dtype, hid, N, HW, nh, Hd, od, nd, w1, douts, dscale, packed, dhid, acc, stream);
 }
 
 // ---------------------------------------------------------------- CenterNet heads: sparse-gradient backward

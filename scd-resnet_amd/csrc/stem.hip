@@ -6,7 +6,12 @@
 // multiplies it with the [64 co][64 tap] weight tile: HBM traffic is the input image plus the output.
 // The weight gradient does the same with a [tap][pixel] tile against the output gradient and writes one
 // fp32 64 x 64 partial per split (reduced by scd_wgrad_reduce, T = 1, Ci = 64, cvalid = 49).
+//
+// The rest of the stem is here too: the im2col kernel of the fp32 parity path, BN-apply + ReLU + MaxPool(3,2,1)
+// forward, its backward (two-pass form: a per-pixel window walk and a 2x2-block kernel for even conv outputs) and the
+// one-pass backward, which rebuilds dz per 2x2 block with the same function as the 2x2-block kernel.
 #include <algorithm>
+#include <type_traits>
 
 #include "gemm_common.h"
 #include "scd_common.h"
@@ -15,6 +20,284 @@ namespace {
 SCD_KERNEL_NS_BEGIN
 
 constexpr int KS = 7, KK = 49, SP = 2, PD = 3, CO = 64;
+
+// ---------------------------------------------------------------- stem im2col
+template <typename T>
+__global__ void im2col_stem_kernel(const float* x, T* cols, int N, int H, int W, int Ho, int Wo, int kh, int kw,
+                                   int stride, int pad, int Kpad) {
+    constexpr int E = Vec16<T>::N;
+    const unsigned cpp = Kpad / E;
+    const unsigned total = (unsigned)N * Ho * Wo * cpp;
+    const unsigned HoWo = (unsigned)Ho * Wo;
+    for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+        const unsigned pix = i / cpp;
+        const int ch = (int)(i - pix * cpp);
+        const int n = (int)(pix / HoWo);
+        const int rem = (int)(pix - (unsigned)n * HoWo);
+        const int oh = rem / Wo, ow = rem - (rem / Wo) * Wo;
+        float v[E];
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+            const int k = ch * E + e;
+            float val = 0.f;
+            if (k < kh * kw) {
+                const int r = k / kw, s = k - (k / kw) * kw;
+                const int ih = oh * stride - pad + r, iw = ow * stride - pad + s;
+                if ((unsigned)ih < (unsigned)H && (unsigned)iw < (unsigned)W) val = x[((long)n * H + ih) * W + iw];
+            }
+            v[e] = val;
+        }
+        Vec16<T>::store(cols + (size_t)pix * Kpad + ch * E, v);
+    }
+}
+
+// ---------------------------------------------------------------- stem BN+ReLU+MaxPool(3,2,1)
+// One thread = one 16-B channel chunk of SPR consecutive pooled rows at one pooled column: it loads the 2 SPR + 1 conv
+// rows x 3 conv columns of those windows at once (clamped addresses; taps outside the image never win).  Conv row
+// 2 oh + 1 is the bottom of window oh and the top of window oh + 1, so one row per thread fetches 1.5x the conv output
+// (PMC, round 4) and four rows per thread 9/8 -- but in the step the conv output was just written and is read back
+// from the Infinity Cache, and the four-row build (203 VGPRs, 2 waves per SIMD) measured 99 us against 82 us for one
+// row per thread (round 5, tools/gpu_abn.sh): one row per thread stays.
+// workgroups of 256 per CU the pool is compiled for (registers: the window loads in flight per thread)
+#ifndef STEM_POOL_OCC
+#define STEM_POOL_OCC 4
+#endif
+#ifndef STEM_SPR
+#define STEM_SPR 1
+#endif
+constexpr int SPR = STEM_SPR;                       // pooled rows per thread
+template <typename T>
+__global__ __launch_bounds__(256, STEM_POOL_OCC) void stem_pool_fwd_kernel(const T* y, const float* scale, const float* shift, T* out, uint8_t* argmax,
+                                     int N, int H, int W, int C, int Ho, int Wo) {
+    constexpr int E = Vec16<T>::N;
+    constexpr int NR = 2 * SPR + 1;
+    const unsigned cpp = C / E;
+    const unsigned G = (unsigned)(Ho + SPR - 1) / SPR;
+    const unsigned GW = G * (unsigned)Wo;
+    const unsigned total = (unsigned)N * GW * cpp;
+    for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+        const unsigned item = i / cpp;
+        const int ch = (int)(i - item * cpp);
+        const int n = (int)(item / GW);
+        const unsigned rem = item - (unsigned)n * GW;
+        const int g = (int)(rem / (unsigned)Wo), ow = (int)(rem - (unsigned)g * Wo);
+        const int oh0 = g * SPR;
+        float sc[E], sh[E];
+#pragma unroll
+        for (int e = 0; e < E; ++e) { sc[e] = scale[ch * E + e]; sh[e] = shift[ch * E + e]; }
+        uint4 raw[NR][3];
+#pragma unroll
+        for (int r = 0; r < NR; ++r)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const int h = min(max(2 * oh0 - 1 + r, 0), H - 1), w = min(max(2 * ow - 1 + c, 0), W - 1);
+                raw[r][c] = *(const uint4*)(y + (((long)n * H + h) * W + w) * C + ch * E);
+            }
+#pragma unroll
+        for (int j = 0; j < SPR; ++j) {
+            const int oh = oh0 + j;
+            float best[E];
+            int arg[E];
+#pragma unroll
+            for (int e = 0; e < E; ++e) { best[e] = -INFINITY; arg[e] = 0; }
+            // the window in window order (first maximum wins, as before)
+#pragma unroll
+            for (int d = 0; d < 9; ++d) {
+                const bool in = (unsigned)(2 * oh - 1 + d / 3) < (unsigned)H && (unsigned)(2 * ow - 1 + d % 3) < (unsigned)W;
+                float v[E];
+                Vec16<T>::load(&raw[2 * j + d / 3][d % 3], v);
+#pragma unroll
+                for (int e = 0; e < E; ++e) {
+                    const float z = in ? fmaxf(v[e] * sc[e] + sh[e], 0.f) : -INFINITY;
+                    if (z > best[e]) { best[e] = z; arg[e] = d; }
+                }
+            }
+            if (oh < Ho) {
+                const size_t pix = ((size_t)n * Ho + oh) * Wo + ow;
+                Vec16<T>::store(out + pix * C + ch * E, best);
+                // the E argmax bytes of this chunk in one store
+                unsigned lo = 0, hi = 0;
+#pragma unroll
+                for (int e = 0; e < E && e < 4; ++e) lo |= (unsigned)arg[e] << (8 * e);
+#pragma unroll
+                for (int e = 4; e < E; ++e) hi |= (unsigned)arg[e] << (8 * (e - 4));
+                if constexpr (E == 8) *(uint2*)(argmax + pix * C + ch * E) = make_uint2(lo, hi);
+                else *(unsigned*)(argmax + pix * C + ch * E) = lo;
+            }
+        }
+    }
+}
+
+// ---- MaxPool(3,2,1) + ReLU backward.  The argmax bytes of a 16-B channel chunk travel as one word (E = 4) or two
+// (E = 8); a pooled output outside the image carries 0xff bytes, which match no window position.
+template <int E> using am_word = std::conditional_t<E == 8, uint2, unsigned>;
+__device__ __forceinline__ unsigned am_byte(unsigned w, int e) { return (w >> (8 * e)) & 0xffu; }
+__device__ __forceinline__ unsigned am_byte(uint2 w, int e) { return am_byte(e < 4 ? w.x : w.y, e & 3); }
+__device__ __forceinline__ unsigned am_or_none(unsigned w, bool ok) { return ok ? w : 0xffffffffu; }
+__device__ __forceinline__ uint2 am_or_none(uint2 w, bool ok) { return ok ? w : make_uint2(0xffffffffu, 0xffffffffu); }
+// g[e] += d[e] where the chunk's argmax byte e names window position sel.  A select, not a branch (as
+// `if (hit) g += d` the compiler emitted 63 exec-masked branch regions per tile of stem_bwd_fused_kernel); g is
+// never -0, so adding +0 leaves it unchanged
+template <typename T, typename AW>
+__device__ __forceinline__ void pool_bwd_take(const void* dvec, AW am, unsigned sel, float* g) {
+    constexpr int E = Vec16<T>::N;
+    float d[E];
+    Vec16<T>::load(dvec, d);
+#pragma unroll
+    for (int e = 0; e < E; ++e) g[e] += am_byte(am, e) == sel ? d[e] : 0.f;
+}
+// ReLU mask of the gathered gradient g by the BN output of y, the stored (rounded) dz chunk, and the BN backward
+// sums of the value the apply pass will see (that stored dz) where STATS
+template <typename T, bool STATS = true>
+__device__ __forceinline__ void pool_bwd_mask(const float* g, const float* v, const float* sc, const float* sh,
+                                              const float* mu, const float* is, void* dz, float* s1, float* s2) {
+    constexpr int E = Vec16<T>::N;
+    float m[E];
+#pragma unroll
+    for (int e = 0; e < E; ++e) m[e] = v[e] * sc[e] + sh[e] > 0.f ? g[e] : 0.f;
+    Vec16<T>::store(dz, m);
+    if constexpr (STATS) {
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+            const float r = to_f<T>(from_f<T>(m[e]));
+            s1[e] += r;
+            s2[e] += r * (v[e] - mu[e]) * is[e];
+        }
+    }
+}
+
+// dz of the 2x2 conv block (2oh + a, 2ow + b) of an even conv output, one 16-B channel chunk: those four pixels are
+// covered only by the pooled outputs O[i][j] = (oh + i, ow + j), and pixel (a, b) sits at window position
+// di = a - 2i + 1, dj = b - 2j + 1 of O[i][j].  Takes values and loads nothing: rd / ra / ry are the raw pooled
+// gradients, argmax words (am_or_none for an O outside the image) and conv outputs; sums run over the outputs in
+// (i, j) order, as the window walk's loops do.  s1 / s2 accumulate.
+template <typename T, typename AW>
+__device__ __forceinline__ void pool_bwd_block2x2(const uint4 (&rd)[2][2], const AW (&ra)[2][2], const uint4 (&ry)[2][2],
+                                                  const float* sc, const float* sh, const float* mu, const float* is,
+                                                  uint4 (&dz)[2][2], float* s1, float* s2) {
+    constexpr int E = Vec16<T>::N;
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            float g[E], v[E];
+#pragma unroll
+            for (int e = 0; e < E; ++e) g[e] = 0.f;
+#pragma unroll
+            for (int oi = 0; oi <= a; ++oi)
+#pragma unroll
+                for (int oj = 0; oj <= b; ++oj)
+                    pool_bwd_take<T>(&rd[oi][oj], ra[oi][oj], (a - 2 * oi + 1) * 3 + (b - 2 * oj + 1), g);
+            Vec16<T>::load(&ry[a][b], v);
+            pool_bwd_mask<T>(g, v, sc, sh, mu, is, &dz[a][b], s1, s2);
+        }
+}
+
+// The two-pass form's backward for any conv output size: one thread per conv pixel and 16-B channel chunk walks the
+// <= 2 x 2 pooled windows that hold the pixel.  The grid stride is a multiple of the chunks per pixel (256 % cpp == 0),
+// so a thread always owns the same E channels and holds their BN parameters in registers.  STATS: the same pass
+// accumulates sum dz and sum dz*(y-mean)*invstd per channel (fp64 replica slots), so the separate reduce pass over dz
+// and y is gone.
+struct PoolBnSums { const float* mean; const float* invstd; double* stats; };
+struct PoolNoSums {};
+template <typename T, bool STATS>
+__global__ __launch_bounds__(256) void stem_pool_bwd_kernel(const T* dout, const uint8_t* argmax, const T* y,
+                                                            const float* scale, const float* shift, T* dz,
+                                                            std::conditional_t<STATS, PoolBnSums, PoolNoSums> bn, int N,
+                                                            int H, int W, int C, int Ho, int Wo) {
+    constexpr int E = Vec16<T>::N;
+    const unsigned cpp = C / E;
+    const unsigned total = (unsigned)N * H * W * cpp;
+    const unsigned HW = (unsigned)H * W;
+    const int ch = (int)(threadIdx.x % cpp);
+    float sc[E], sh[E], mu[E], is[E], s1[E], s2[E];
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        sc[e] = scale[ch * E + e]; sh[e] = shift[ch * E + e];
+        if constexpr (STATS) { mu[e] = bn.mean[ch * E + e]; is[e] = bn.invstd[ch * E + e]; s1[e] = 0.f; s2[e] = 0.f; }
+    }
+    for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+        const size_t pix = i / cpp;
+        const int n = (int)((unsigned)pix / HW);
+        const int rem = (int)((unsigned)pix - (unsigned)n * HW);
+        const int h = rem / W, w = rem - (rem / W) * W;
+        float g[E], v[E];
+#pragma unroll
+        for (int e = 0; e < E; ++e) g[e] = 0.f;
+        const int oh0 = h / 2, oh1 = min(Ho - 1, (h + 1) / 2);
+        const int ow0 = w / 2, ow1 = min(Wo - 1, (w + 1) / 2);
+        for (int oh = oh0; oh <= oh1; ++oh) {
+            const int di = h - (2 * oh - 1);
+            if (di < 0 || di > 2) continue;
+            for (int ow = ow0; ow <= ow1; ++ow) {
+                const int dj = w - (2 * ow - 1);
+                if (dj < 0 || dj > 2) continue;
+                const long o = (((long)n * Ho + oh) * Wo + ow) * C + ch * E;
+                pool_bwd_take<T>(dout + o, *(const am_word<E>*)(argmax + o), di * 3 + dj, g);
+            }
+        }
+        Vec16<T>::load(y + pix * C + ch * E, v);
+        pool_bwd_mask<T, STATS>(g, v, sc, sh, mu, is, dz + pix * C + ch * E, s1, s2);
+    }
+    if constexpr (STATS) {
+        __shared__ float red[2][256][E + 1];
+        channel_sums_to_slots<E>(s1, s2, &red[0][0][0], C, cpp, bn.stats);
+    }
+}
+
+// The same pass for even inputs (H = 2 Ho, W = 2 Wo), one thread per 2x2 input block and 16-B channel chunk (see
+// pool_bwd_block2x2): the thread issues its 4 gradient vectors, 4 argmax words and 4 activation vectors together (no
+// data-dependent branches around loads; out-of-range pooled outputs read O[0][0] and are ignored) and each pooled
+// gradient is read ~once per 4 inputs.
+template <typename T>
+__global__ __launch_bounds__(256) void stem_pool_bwd_bn_2x2_kernel(const T* dout, const uint8_t* argmax, const T* y,
+                                                                   const float* scale, const float* shift,
+                                                                   const float* mean, const float* invstd, T* dz,
+                                                                   double* stats, int N, int C, int Ho, int Wo) {
+    constexpr int E = Vec16<T>::N;
+    const unsigned cpp = C / E;
+    const unsigned total = (unsigned)N * Ho * Wo * cpp;
+    const unsigned HWo = (unsigned)Ho * Wo;
+    const int W = 2 * Wo;
+    const int ch = (int)(threadIdx.x % cpp);
+    float sc[E], sh[E], mu[E], is[E], s1[E], s2[E];
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        sc[e] = scale[ch * E + e]; sh[e] = shift[ch * E + e]; mu[e] = mean[ch * E + e]; is[e] = invstd[ch * E + e];
+        s1[e] = 0.f; s2[e] = 0.f;
+    }
+    for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+        const unsigned blk = i / cpp;
+        const unsigned n = blk / HWo;
+        const unsigned rem = blk - n * HWo;
+        const int oh = (int)(rem / Wo), ow = (int)(rem - (rem / Wo) * Wo);
+        const bool okh = oh + 1 < Ho, okw = ow + 1 < Wo;
+        uint4 rd[2][2], ry[2][2], o[2][2];
+        am_word<E> ra[2][2];
+#pragma unroll
+        for (int oi = 0; oi < 2; ++oi)
+#pragma unroll
+            for (int oj = 0; oj < 2; ++oj) {
+                const bool ok = (oi == 0 || okh) && (oj == 0 || okw);
+                const unsigned p = ((n * Ho + oh + (ok ? oi : 0)) * Wo + ow + (ok ? oj : 0)) * C + ch * E;
+                rd[oi][oj] = *(const uint4*)(dout + p);
+                ra[oi][oj] = am_or_none(*(const am_word<E>*)(argmax + p), ok);
+            }
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int b = 0; b < 2; ++b)
+                ry[a][b] = *(const uint4*)(y + ((n * (2 * Ho) + 2 * oh + a) * W + 2 * ow + b) * (unsigned)C + ch * E);
+        pool_bwd_block2x2<T>(rd, ra, ry, sc, sh, mu, is, o, s1, s2);
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int b = 0; b < 2; ++b)
+                *(uint4*)(dz + ((n * (2 * Ho) + 2 * oh + a) * W + 2 * ow + b) * (unsigned)C + ch * E) = o[a][b];
+    }
+    __shared__ float red[2][256][E + 1];
+    channel_sums_to_slots<E>(s1, s2, &red[0][0][0], C, cpp, stats);
+}
 
 // ---- forward: one workgroup = 2 output rows x 128 output columns (256 pixels) of one image
 constexpr int FTW = 128, FTH = 2;
@@ -294,8 +577,8 @@ __global__ __launch_bounds__(256) void stem_conv_wgrad_kernel(const h16* __restr
 // (scd_bn_bwd_finalize's coefficients, which need the batch sums of dz and dz*xhat first), the weight gradient is
 //     dW = sum_p dy[p] col[p]^T = a * T1 + b * W G + c * s,   T1 = sum_p dz[p] col[p]^T,  G = sum_p col[p] col[p]^T,
 // s = sum_p col[p] (tap 49 of col is 1, so s = G[.][49]).  One pass therefore rebuilds dz per 2x2 conv block from
-// the pooled gradient / argmax / y (as stem_pool_bwd_bn_2x2_kernel), accumulates the BN backward sums, and runs the
-// T1 and G MFMAs on an LDS tile of dz and the [tap][pixel] input columns: dz is never written to HBM and y is read
+// the pooled gradient / argmax / y (pool_bwd_block2x2, as stem_pool_bwd_bn_2x2_kernel does), accumulates the BN
+// backward sums, and runs the T1 and G MFMAs on an LDS tile of dz and the [tap][pixel] input columns: dz is never written to HBM and y is read
 // once (the unfused backward wrote dz and read it, and y, again).  Tile = 2 conv rows x 64 columns (32 2x2 blocks
 // x 8 channel chunks = one item per thread).  W G uses the conv's bf16 weights in fp32 (the forward multiplied
 // the same operands), so dW matches the unfused path up to the bf16 rounding of y and dy that it no longer has.
@@ -398,7 +681,8 @@ __global__ __launch_bounds__(256, 2) void stem_bwd_fused_kernel(
     };
     if (t0 < t1) load_tile(t0, false);
     for (int t = t0; t < t1; ++t) {
-        // ---- dz of the 2x2 conv block (2bo + a, 2bc + b), channels 8ch .. 8ch+7
+        // ---- dz of the 2x2 conv block (2bo + a, 2bc + b), channels 8ch .. 8ch+7: pool_bwd_block2x2's arithmetic in
+        // this kernel's own text (through the function, in any of eight forms tried, 234 VGPRs against 230 here)
 #pragma unroll
         for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -419,8 +703,7 @@ __global__ __launch_bounds__(256, 2) void stem_bwd_fused_kernel(
 #pragma unroll
                         for (int e = 0; e < 8; ++e) {
                             const bool hit = ((aw[e >> 2] >> (8 * (e & 3))) & 0xffu) == sel;
-                            // a select, not a branch (as `if (hit) g += d` the compiler emitted 63 exec-masked
-                            // branch regions per tile); g is never -0, so adding +0 leaves it unchanged
+                            // (the select of pool_bwd_take)
                             g[e] += hit ? d[e] : 0.f;
                         }
                     }
@@ -513,17 +796,7 @@ __global__ __launch_bounds__(256, 2) void stem_bwd_fused_kernel(
             *(f32x4*)(wz + CO * 64 + (wm * 32 + i * 16 + l16) * 64 + wn * 32 + b * 16 + lg * 4) = acc2[i][b];
         }
     // ---- BN backward sums: threads with equal tid % 8 hold the same channels
-    float* red = (float*)smem;                        // [2][256][9]
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { red[tid * 9 + e] = s1[e]; red[(256 + tid) * 9 + e] = s2[e]; }
-    __syncthreads();
-    if (tid < 2 * CO) {
-        const int stat = tid / CO, c = tid - (tid / CO) * CO;
-        const int cc = c / 8, e = c - (c / 8) * 8;
-        double acc = 0.0;
-        for (int t = cc; t < 256; t += 8) acc += red[(stat * 256 + t) * 9 + e];
-        atomic_add_f64(stat_slot(stats, stat_replica(blockIdx.x), stat, CO, c), acc);
-    }
+    channel_sums_to_slots<8>(s1, s2, (float*)smem, CO, 8, stats);
 }
 
 // sum of the per-split [T1 | G] slabs in a fixed order: workgroup = 32 consecutive elements x 8 split lanes (each
@@ -573,14 +846,90 @@ __global__ __launch_bounds__(64) void stem_bwd_combine_kernel(const float* __res
 }
 
 
+// (Ho, Wo) is the output of Conv2d(1, 64, 7, stride 2, pad 3) on (H, W)
+inline bool stem_geom_ok(int H, int W, int Ho, int Wo) {
+    return Ho == (H + 2 * PD - KS) / SP + 1 && Wo == (W + 2 * PD - KS) / SP + 1;
+}
+
+// (as layers.hip's: block_ops.h caps its grids at 4096)
+inline int ew_blocks(long n) { return (int)std::min<long>(8192, std::max<long>(1, (n + 255) / 256)); }
+
 SCD_KERNEL_NS_END
 }  // namespace
+
+extern "C" int scd_im2col_stem(int dtype, const float* x, void* cols, int N, int H, int W, int Ho, int Wo, int kh,
+                               int kw, int stride, int pad, int Kpad, void* stream) {
+    SCD_F16_FWD(scd_im2col_stem, x, cols, N, H, W, Ho, Wo, kh, kw, stride, pad, Kpad, stream);
+    if (Kpad % 8 || Kpad < kh * kw) return SCD_ERR_ARG;
+    return scd_dispatch_dtype(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        constexpr int E = 16 / sizeof(T);
+        const long total = (long)N * Ho * Wo * (Kpad / E);
+        hipLaunchKernelGGL((im2col_stem_kernel<T>), dim3(ew_blocks(total)), dim3(256), 0, (hipStream_t)stream, x,
+                           (T*)cols, N, H, W, Ho, Wo, kh, kw, stride, pad, Kpad);
+        SCD_RETURN_LAUNCH();
+    });
+}
+
+extern "C" int scd_stem_pool_fwd(int dtype, const void* y, const float* scale, const float* shift, void* out,
+                                 uint8_t* argmax, int N, int H, int W, int C, int Ho, int Wo, void* stream) {
+    SCD_F16_FWD(scd_stem_pool_fwd, y, scale, shift, out, argmax, N, H, W, C, Ho, Wo, stream);
+    return scd_dispatch_dtype(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        constexpr int E = 16 / sizeof(T);
+        if (C % E) return SCD_ERR_ARG;
+        const long total = (long)N * ((Ho + SPR - 1) / SPR) * Wo * (C / E);
+        if (total >= (1L << 32)) return SCD_ERR_ARG;
+        hipLaunchKernelGGL((stem_pool_fwd_kernel<T>), dim3(ew_blocks(total)), dim3(256), 0, (hipStream_t)stream,
+                           (const T*)y, scale, shift, (T*)out, argmax, N, H, W, C, Ho, Wo);
+        SCD_RETURN_LAUNCH();
+    });
+}
+
+extern "C" int scd_stem_pool_bwd(int dtype, const void* dout, const uint8_t* argmax, const void* y, const float* scale,
+                                 const float* shift, void* dz, int N, int H, int W, int C, int Ho, int Wo, void* stream) {
+    SCD_F16_FWD(scd_stem_pool_bwd, dout, argmax, y, scale, shift, dz, N, H, W, C, Ho, Wo, stream);
+    return scd_dispatch_dtype(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        constexpr int E = 16 / sizeof(T);
+        if (C % E || 256 % (C / E)) return SCD_ERR_ARG;
+        const long total = (long)N * H * W * (C / E);
+        hipLaunchKernelGGL((stem_pool_bwd_kernel<T, false>), dim3(ew_blocks(total)), dim3(256), 0, (hipStream_t)stream,
+                           (const T*)dout, argmax, (const T*)y, scale, shift, (T*)dz, PoolNoSums{}, N, H, W, C, Ho, Wo);
+        SCD_RETURN_LAUNCH();
+    });
+}
+
+extern "C" int scd_stem_pool_bwd_bn(int dtype, const void* dout, const uint8_t* argmax, const void* y, const float* scale,
+                                    const float* shift, const float* mean, const float* invstd, void* dz, double* stats,
+                                    int N, int H, int W, int C, int Ho, int Wo, void* stream) {
+    SCD_F16_FWD(scd_stem_pool_bwd_bn, dout, argmax, y, scale, shift, mean, invstd, dz, stats, N, H, W, C, Ho, Wo, stream);
+    return scd_dispatch_dtype(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        constexpr int E = 16 / sizeof(T);
+        hipStream_t st = (hipStream_t)stream;
+        if (C % E || 256 % (C / E)) return SCD_ERR_ARG;
+        const long total = (long)N * H * W * (C / E);
+        if (H == 2 * Ho && W == 2 * Wo && (long)N * H * W * C < (1L << 31)) {
+            static const int g2 = resident_grid((const void*)stem_pool_bwd_bn_2x2_kernel<T>, 256);
+            const long blocks2 = (long)N * Ho * Wo * (C / E);
+            const int grid = (int)std::min<long>(g2, (blocks2 + 255) / 256);
+            hipLaunchKernelGGL((stem_pool_bwd_bn_2x2_kernel<T>), dim3(grid), dim3(256), 0, st, (const T*)dout, argmax,
+                               (const T*)y, scale, shift, mean, invstd, (T*)dz, stats, N, C, Ho, Wo);
+            SCD_RETURN_LAUNCH();
+        }
+        static const int g = resident_grid((const void*)stem_pool_bwd_kernel<T, true>, 256);
+        const int blocks = (int)std::min<long>(g, (total + 255) / 256);
+        hipLaunchKernelGGL((stem_pool_bwd_kernel<T, true>), dim3(blocks), dim3(256), 0, st, (const T*)dout, argmax,
+                           (const T*)y, scale, shift, (T*)dz, PoolBnSums{mean, invstd, stats}, N, H, W, C, Ho, Wo);
+        SCD_RETURN_LAUNCH();
+    });
+}
 
 extern "C" int scd_stem_conv_fwd(int dtype, const float* x, const void* wpk, void* y, double* stats, int N, int H,
                                  int W, int Ho, int Wo, void* stream) {
     SCD_F16_FWD(scd_stem_conv_fwd, x, wpk, y, stats, N, H, W, Ho, Wo, stream);
-    if (dtype != SCD_DT_BF16 || N <= 0 || Ho != (H + 2 * PD - KS) / SP + 1 || Wo != (W + 2 * PD - KS) / SP + 1 ||
-        Wo % FTW || Ho % FTH || !y)
+    if (dtype != SCD_DT_BF16 || N <= 0 || !stem_geom_ok(H, W, Ho, Wo) || Wo % FTW || Ho % FTH || !y)
         return SCD_ERR_ARG;
     // one workgroup per tile (a resident-grid walk with the next tile's patch in flight and the weights in registers
     // measured slower, 121 vs 106 us: the kernel is bound by its LDS / VALU tile build, not by load latency)
@@ -593,8 +942,7 @@ extern "C" int scd_stem_conv_fwd(int dtype, const float* x, const void* wpk, voi
 extern "C" int scd_stem_conv_wgrad(int dtype, const void* dy, const void* ybn, const float* coef, const float* x,
                                    float* ws, int nsplit, int N, int H, int W, int Ho, int Wo, void* stream) {
     SCD_F16_FWD(scd_stem_conv_wgrad, dy, ybn, coef, x, ws, nsplit, N, H, W, Ho, Wo, stream);
-    if (dtype != SCD_DT_BF16 || nsplit < 1 || Wo % WPX || Ho != (H + 2 * PD - KS) / SP + 1 ||
-        Wo != (W + 2 * PD - KS) / SP + 1)
+    if (dtype != SCD_DT_BF16 || nsplit < 1 || Wo % WPX || !stem_geom_ok(H, W, Ho, Wo))
         return SCD_ERR_ARG;
     const long M = (long)N * Ho * Wo;
     long chunk = (M + nsplit - 1) / nsplit;
@@ -612,8 +960,8 @@ extern "C" int scd_stem_bwd_fused(int dtype, const void* dout, const uint8_t* ar
                                   void* stream) {
     SCD_F16_FWD(scd_stem_bwd_fused, dout, argmax, y, scale, shift, mean, invstd, x, stats, ws, nsplit, tg, N, H, W, Ho,
                 Wo, stream);
-    if (dtype != SCD_DT_BF16 || nsplit < 1 || Wo % BTW || Ho % 2 || Ho != (H + 2 * PD - KS) / SP + 1 ||
-        Wo != (W + 2 * PD - KS) / SP + 1 || (long)N * Ho * Wo * CO >= (1L << 31))
+    if (dtype != SCD_DT_BF16 || nsplit < 1 || Wo % BTW || Ho % 2 || !stem_geom_ok(H, W, Ho, Wo) ||
+        (long)N * Ho * Wo * CO >= (1L << 31))
         return SCD_ERR_ARG;
     const int ntiles = N * (Ho / 2) * (Wo / BTW);
     const int chunk = (ntiles + nsplit - 1) / nsplit;

@@ -1418,10 +1418,15 @@ def im2col_stem(x, dtype, kh=7, kw=7, stride=2, pad=3, Kpad=64):
     return cols
 
 
+def _stem_out_hw(H, W):
+    """Output size of the stem's Conv2d(1,64,7,s2,p3)."""
+    return (H + 6 - 7) // 2 + 1, (W + 6 - 7) // 2 + 1
+
+
 def stem_direct_ok(x, dtype):
     """The direct stem kernels (bf16; Conv2d(1,64,7,s2,p3) with an output width that is a multiple of 128)."""
     N, _, H, W = x.shape
-    Ho, Wo = (H + 6 - 7) // 2 + 1, (W + 6 - 7) // 2 + 1
+    Ho, Wo = _stem_out_hw(H, W)
     return dtype in HALF and Wo % 128 == 0 and Ho % 2 == 0
 
 
@@ -1429,7 +1434,7 @@ def stem_conv_fwd(x, wpk, stats=None):
     """Conv2d(1,64,7,s2,p3) of NCHW fp32 x -> (N,Ho,Wo,64) bf16 NHWC (+BN sums); wpk = pack_weight(w, bf16, 0, ldp=64)."""
     _need_gpu(x)
     N, _, H, W = x.shape
-    Ho, Wo = (H + 6 - 7) // 2 + 1, (W + 6 - 7) // 2 + 1
+    Ho, Wo = _stem_out_hw(H, W)
     y = torch.empty(N, Ho, Wo, 64, dtype=wpk.dtype, device=x.device)
     L.call("scd_stem_conv_fwd", dt(wpk), ptr(x), ptr(wpk), ptr(y), ptr(stats), N, H, W, Ho, Wo, stream())
     return y
@@ -1449,8 +1454,8 @@ def stem_fwd(x, wpk, geom, dtype, stats=None):
 
 def stem_out_count(x):
     """Pixels of the stem conv output per channel (the BN count)."""
-    H, W = x.shape[2], x.shape[3]
-    return x.shape[0] * ((H + 6 - 7) // 2 + 1) * ((W + 6 - 7) // 2 + 1)
+    Ho, Wo = _stem_out_hw(x.shape[2], x.shape[3])
+    return x.shape[0] * Ho * Wo
 
 
 def stem_conv_wgrad(dy, x, dst, accumulate=True, ybn=None, coef=None):
@@ -1494,7 +1499,7 @@ def stem_backward_fused(bn, dout, am, y, st, x, wpk, dst):
     gradient a*T1 + b*W G + c*s; the full-resolution dz is never materialised."""
     N, C = y.shape[0], y.shape[3]
     H, W = x.shape[2], x.shape[3]
-    Ho, Wo = (H + 6 - 7) // 2 + 1, (W + 6 - 7) // 2 + 1
+    Ho, Wo = _stem_out_hw(H, W)
     ns = L.lib().scd_stem_bwd_nsplit()
     ws = torch.empty(ns * 2 * 64 * 64, dtype=torch.float32, device=y.device)
     tg = torch.empty(2 * 64 * 64, dtype=torch.float32, device=y.device)

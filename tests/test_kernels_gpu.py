@@ -521,6 +521,69 @@ def test_stem_pool_forward_matches_torch(shape, dtype):
     assert torch.equal(ga[clear], arg[clear])
 
 
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16, torch.float32])
+@pytest.mark.parametrize("shape", [(1, 7, 9), (3, 5, 8), (2, 6, 8), (1, 2, 2)])
+def test_stem_pool_backward_small(shape, dtype):
+    """scd_stem_pool_bwd and scd_stem_pool_bwd_bn (MaxPool(3, 2, 1) + ReLU backward, the second with the BN backward
+    sums) against a float64 scatter of the pooled gradient by the forward kernel's own argmax, at the sizes where the
+    kernels' paths part: (1, 7, 9) and (3, 5, 8) take the per-pixel window walk (an odd side: ragged windows on both
+    edges / on one), (2, 6, 8) the 2x2-block kernel with a last block row and column that have no neighbour, (1, 2, 2)
+    the 2x2-block kernel with one pooled pixel (every neighbour out of range).  C = 64: 16 chunks per pixel in fp32,
+    8 in the 16-bit types.  dz within one rounding of the dtype (the forward test's bound); the two entry points'
+    dz equal bit for bit; the sums against float64 sums of the stored dz to 1e-5, as the other stem tests hold them."""
+    from scdhip import lib as L
+    from scdhip import ops
+    N, H, W = shape
+    C = 64
+    g = torch.Generator().manual_seed(31)
+    y = torch.randn(N, H, W, C, generator=g).to(dtype).to(DEV)
+    bn = torch.nn.BatchNorm2d(C).to(DEV)
+    st = ops.BNState()
+    st.scale = (torch.rand(C, generator=g) + 0.5).to(DEV)
+    st.shift = torch.randn(C, generator=g).to(DEV)
+    st.mean = torch.randn(C, generator=g).to(DEV)
+    st.invstd = (torch.rand(C, generator=g) + 0.5).to(DEV)
+    st.count = N * H * W
+    out, am = ops.stem_pool_fwd(y, st)
+    Ho, Wo = out.shape[1], out.shape[2]
+    dout = torch.randn(N, Ho, Wo, C, generator=g).to(dtype).to(DEV)
+    # float64 reference: every pooled gradient goes to the conv pixel its argmax byte names; ReLU mask
+    n, oh, ow, c = torch.meshgrid(torch.arange(N), torch.arange(Ho), torch.arange(Wo), torch.arange(C), indexing="ij")
+    a = am.long().cpu()
+    h, w = 2 * oh - 1 + a // 3, 2 * ow - 1 + a % 3
+    assert (a < 9).all() and (h >= 0).all() and (h < H).all() and (w >= 0).all() and (w < W).all()
+    ref = torch.zeros(N, H, W, C, dtype=torch.float64)
+    ref.index_put_((n, h, w, c), dout.double().cpu(), accumulate=True)
+    yd = y.double().cpu()
+    ref[yd * st.scale.double().cpu() + st.shift.double().cpu() <= 0] = 0
+    ulp = {torch.bfloat16: 2.0 ** -7, torch.float16: 2.0 ** -10, torch.float32: 2.0 ** -23}[dtype]
+
+    dz = ops.stem_pool_bwd(dout, am, y, st)
+    dz_bn, _ = ops.stem_pool_bwd_bn(bn, dout, am, y, st)
+    # the same entry point once more into the layer's (re-zeroed) statistics buffer, read before any finalize
+    stats = ops.bn_stats(bn, "bwd")
+    assert torch.count_nonzero(stats) == 0
+    dz_st = torch.empty_like(y)
+    L.call("scd_stem_pool_bwd_bn", ops.dt(y), ops.ptr(dout), ops.ptr(am), ops.ptr(y), ops.ptr(st.scale),
+           ops.ptr(st.shift), ops.ptr(st.mean), ops.ptr(st.invstd), ops.ptr(dz_st), ops.ptr(stats), N, H, W, C, Ho, Wo,
+           ops.stream())
+    torch.cuda.synchronize()
+    sums = stats.view(-1, 2, C).sum(0).cpu()
+    stats.zero_()
+    for got in (dz, dz_bn):
+        err = (got.double().cpu() - ref).abs()
+        print("stem pool backward %s %s: max error %.3g" % (shape, dtype, err.max().item()))
+        assert (err <= ulp * ref.abs() + 4e-6).all()
+    assert torch.equal(dz, dz_bn) and torch.equal(dz, dz_st)
+    zd = dz_bn.double().cpu()
+    xhat = (yd - st.mean.double().cpu()) * st.invstd.double().cpu()
+    e1, e2 = rel_err(sums[0], zd.sum((0, 1, 2))), rel_err(sums[1], (zd * xhat).sum((0, 1, 2)))
+    print("stem pool backward %s %s: sum dz %.3g, sum dz*xhat %.3g" % (shape, dtype, e1, e2))
+    assert e1 < 1e-5 and e2 < 1e-5
+    # ... and through the finalize: dbeta = sum dz, dgamma = sum dz*xhat
+    assert rel_err(bn.bias.grad, zd.sum((0, 1, 2))) < 1e-5 and rel_err(bn.weight.grad, (zd * xhat).sum((0, 1, 2))) < 1e-5
+
+
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("shape", [(2, 512, 512), (3, 260, 256)])
 def test_stem_one_pass_backward(shape, dtype):

@@ -1,5 +1,5 @@
 """Time the stem kernels at the Res10 B=32 512^2 shape: conv (+BN statistics), BN-apply+ReLU+max-pool, pool backward
-(+BN backward sums) and the weight gradient (+BN backward apply) (stem.hip, layers.hip), HIP events.
+(with and without the BN backward sums) and the weight gradient (+BN backward apply) (stem.hip), HIP events.
 
 python tools/stem_bench.py [--reps 20] [--batch 32]
 """
@@ -58,6 +58,8 @@ def main():
     dz, coef = ops.stem_pool_bwd_bn(bn, dout, am, y, st)
     rep("stem_conv_wgrad (+BN apply)", timed(lambda: ops.stem_conv_wgrad(dz, x, dw, ybn=y, coef=coef), a.reps))
     print("chain %.1f us" % sum(us for _, us in rows))
+    # the pool backward without the BN sums (the fp32 parity path's; not part of the chain)
+    rep("stem_pool_bwd", timed(lambda: ops.stem_pool_bwd(dout, am, y, st), a.reps))
     # the one-pass backward the model runs (scd_stem_bwd_fused + reduce + BN finalize + combine)
     rep("stem_backward_fused (one pass)", timed(lambda: ops.stem_backward_fused(bn, dout, am, y, st, x, wpk, dw),
                                                 a.reps))
