@@ -77,6 +77,16 @@ int scd_conv_gemm_bnbwd(int dtype, const void* x, const void* w, void* y, int N,
                         int Wo, int Co, int in_stride, int out_stride, int wrow, int nphase,
                         const scd_gemm_phase* phases, const void* bn_y, const float* mean, const float* invstd,
                         const float* relu_scale, const float* relu_shift, double* bn_stats, void* stream);
+/* scd_conv_gemm -- or, with bn_y != NULL, scd_conv_gemm_bnbwd with `stats` as its bn_stats (no bias / ReLU /
+ * accumulate then) -- on a named kernel whatever the grid size: kernel 0 the register-staged 128 x 128 tile, 1 the
+ * LDS-DMA ring on the same tile, which the library picks by itself for long-K grids of 256 to 384 tiles.  The two
+ * give the same bits (output and statistics); this entry point exists so that tests can run both on one input.
+ * 16-bit dtypes and Co > 64; SCD_ERR_ARG otherwise. */
+int scd_conv_gemm_sel(int dtype, int kernel, const void* x, const void* w, void* y, const float* bias, double* stats,
+                      int N, int Hi, int Wi, int Ci, int Ho, int Wo, int Co, int in_stride, int out_stride, int wrow,
+                      int relu, int accumulate, int nphase, const scd_gemm_phase* phases, const void* bn_y,
+                      const float* mean, const float* invstd, const float* relu_scale, const float* relu_shift,
+                      void* stream);
 /* Folded-BatchNorm inference conv: y[pix,co] = act(acc + bias[co] + res[pix,co]) with acc the gather-GEMM of
  * scd_conv_gemm.  res is NHWC (N,Ho,Wo,Co) in dtype, read at the output pixel's own offset; the sum is formed in fp32
  * from the unrounded accumulator, the ReLU follows the add and the result is rounded once to dtype at the store

@@ -1068,6 +1068,179 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_ring_kernel(GemmParams p) {
 }
 
 // -------------------------------------------------------------------------------------
+// The same LDS-DMA ring on the 128 x 128 tile of conv_gemm_kernel<T,128,128>, for the grids that are too small for
+// the 256 x 128 tile (8,192 GEMM rows x 512 columns: 256 tiles here, 128 there).  8 waves, one workgroup per CU:
+// wave w owns tile rows 64 (w >> 2) .. +63 x columns 32 (w & 3) .. +31, so each channel's statistics add the four
+// 16-row blocks in one wave in the register-staged kernel's order.  A K-stage is 32 KiB (4 DMA instructions per
+// lane), one raw barrier per stage.  The ring has 4 slots and the wait is vmcnt(8): at 64 FLOP per byte of LDS-DMA
+// the loop is bound by the L2 -> LDS feed, and three stages (96 KiB) in flight per CU measured 7-8 % faster per launch
+// than two; a fifth slot added nothing.
+// KS mirrors the register-staged kernel's intra-workgroup split K, which sums the two halves of the K stages apart
+// and adds them at the end: here the ring alternates between the halves (even steps: stage j into acc, odd steps:
+// stage KTg + j into acc2), so every output sees its products in that kernel's order and the results are
+// bit-identical for KS = 1 and KS = 2.  A half without a live stage left multiplies a zero-filled slot.
+// After the loop the odd waves hand their accumulators to their even neighbours through LDS and exit; the four
+// remaining waves hold 64 x 64 each and run the shared epilogue as the 4-wave kernel does.
+template <int KS, bool BNB = false>
+__global__ __launch_bounds__(512, 1) void conv_gemm_ring128_kernel(GemmParams p) {
+    typedef h16 T;
+    static_assert(KS == 1 || KS == 2, "split K by 1 or 2");
+    constexpr int BM = 128, BN = 128, BK = 64, EPC = 8;
+    constexpr int STAGE = (BM + BN) * 128;          // 32 KiB
+    constexpr int NSLOT = 4;                        // 128 KiB: three stages in flight (below)
+    __shared__ __attribute__((aligned(16))) char smem[NSLOT * STAGE];
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int bid = xcd_tile_id();
+    const GemmTile tile = gemm_tile(p, bid);
+    const scd_gemm_phase& ph = p.ph[tile.phase];
+    const int mt = tile.mt, nt = tile.nt, QQ = tile.QQ, M = tile.M;
+
+    // DMA rows of this lane: A rows 16*wave + 8*i + lane/8, B rows 16*wave + 8*j + lane/8 (i, j < 2); source chunk
+    // swizzled as in the 256 x 128 kernel
+    const int lrow = lane >> 3;
+    const int cch = (lane & 7) ^ (lrow & 7);
+    int a_pix[2], a_ih[2], a_iw[2];
+    bool a_ok[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int m = mt * BM + 16 * wave + 8 * i + lrow;
+        a_ok[i] = m < M;
+        const PixPos q = pix_of(a_ok[i] ? m : 0, QQ, ph.Qw);
+        a_pix[i] = q.n * p.Hi * p.Wi;
+        a_ih[i] = p.is * q.qh;
+        a_iw[i] = p.is * q.qw;
+    }
+    int b_row[2];
+    bool b_ok[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int nn = nt * BN + 16 * wave + 8 * j + lrow;
+        b_ok[j] = nn < p.Co;
+        b_row[j] = b_ok[j] ? nn : 0;
+    }
+    const int cpt = p.Ci / BK;
+    const int ntaps = max(ph.ntaps, 1);             // (a phase without taps has no live stage)
+    const int KT = ph.ntaps * cpt;
+    const int KTg = (KT + KS - 1) / KS;             // stages per half, as conv_gemm_kernel's
+    const int NST = KS * KTg;                       // ring steps
+    const __amdgpu_buffer_rsrc_t xrs = buf_rsrc(p.x, p.xbytes);
+    const __amdgpu_buffer_rsrc_t wrs = buf_rsrc(p.w, p.wbytes);
+
+    struct StageArgs { int live, c0, dh, dw, wt; };
+    // ring step s -> its K stage: s (KS = 1), or stage s / 2 of half s % 2
+    auto stage_args = [&](int s) {
+        StageArgs a;
+        const int kt_req = KS == 1 ? s : (s & 1) * KTg + (s >> 1);
+        a.live = s < NST && kt_req < KT;
+        const int kt = max(0, min(kt_req, KT - 1));
+        const int chunk = kt / ntaps, tap = kt - chunk * ntaps;         // channel chunk outer, taps inner
+        a.c0 = chunk * BK + cch * EPC;
+        a.dh = ph.dh[tap]; a.dw = ph.dw[tap]; a.wt = ph.wt[tap];
+        return a;
+    };
+    // the 4 DMA instructions of one K-stage into ring slot `slot` (always 4: the vmcnt counts are static)
+    auto issue = [&](const StageArgs& g, int slot) {
+        char* As = smem + slot * STAGE;
+        char* Bs = As + BM * 128;
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int ih = a_ih[i] + g.dh, iw = a_iw[i] + g.dw;
+            const bool ok = g.live && a_ok[i] && (unsigned)ih < (unsigned)p.Hi && (unsigned)iw < (unsigned)p.Wi;
+            dma16(xrs, As + (16 * wave + 8 * i) * 128, sel_off(ok, ((a_pix[i] + ih * p.Wi + iw) * p.Ci + g.c0) * 2));
+        }
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+            dma16(wrs, Bs + (16 * wave + 8 * j) * 128,
+                  sel_off(g.live && b_ok[j], (b_row[j] * p.wrow + g.wt * p.Ci + g.c0) * 2));
+    };
+
+    const int wm = wave >> 2, wn = wave & 3;
+    const int l16 = lane & 15, lg = lane >> 4;
+    const int l7 = l16 & 7;
+    f32x4 acc[4][2], acc2[KS == 2 ? 4 : 1][2];
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            acc[a][b] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            if constexpr (KS == 2) acc2[a][b] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        }
+
+    int slot = 0;
+    // one ring step: stage s has landed for every wave after the barrier, stage s + NSLOT - 1 goes into the slot
+    // that stage s - 1 was read from, the 16 MFMAs of stage s go into `c`
+    auto step = [&](int s, f32x4 (&c)[4][2]) {
+        const StageArgs nxt = stage_args(s + NSLOT - 1);
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * (NSLOT - 2)) : "memory");
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        issue(nxt, slot == 0 ? NSLOT - 1 : slot - 1);
+        const char* As = smem + slot * STAGE;
+        const char* Bs = As + BM * 128;
+        h16x8 af[2][4], bfr[2][2];
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const int co = ((k * 4 + lg) ^ l7) << 4;
+#pragma unroll
+            for (int a = 0; a < 4; ++a) af[k][a] = *(const h16x8*)(As + (wm * 64 + a * 16 + l16) * 128 + co);
+#pragma unroll
+            for (int b = 0; b < 2; ++b) bfr[k][b] = *(const h16x8*)(Bs + (wn * 32 + b * 16 + l16) * 128 + co);
+        }
+        __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+        for (int k = 0; k < 2; ++k)
+#pragma unroll
+            for (int a = 0; a < 4; ++a)
+#pragma unroll
+                for (int b = 0; b < 2; ++b) c[a][b] = mfma_16x16x32_h16(bfr[k][b], af[k][a], c[a][b]);
+        __builtin_amdgcn_s_setprio(0);
+        slot = slot == NSLOT - 1 ? 0 : slot + 1;
+    };
+
+#pragma unroll
+    for (int s = 0; s < NSLOT - 1; ++s) issue(stage_args(s), s);
+    for (int s = 0; s < NST; s += KS) {
+        step(s, acc);
+        if constexpr (KS == 2) step(s + 1, acc2);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if constexpr (KS == 2) {
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int b = 0; b < 2; ++b) acc[a][b] += acc2[a][b];
+    }
+    // odd waves -> their even neighbours ([pair][register][lane] floats: conflict-free), which then hold the 64 x 64
+    // sub-tile of wave (wave >> 1) of the 4-wave kernel
+    float* xs = (float*)smem + (wave >> 1) * 32 * 64 + lane;
+    if (wave & 1) {
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int b = 0; b < 2; ++b)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) xs[(a * 8 + b * 4 + r) * 64] = acc[a][b][r];
+    }
+    __syncthreads();
+    if (wave & 1) return;
+    f32x4 full[4][4];
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            full[a][b] = acc[a][b];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) full[a][2 + b][r] = xs[(a * 8 + b * 4 + r) * 64];
+        }
+    __syncthreads();                                 // (the surviving waves: the epilogue stages over xs)
+    gemm_epilogue<T, BM, BN, 2, false, BNB, false>(p, full, smem, ((wave >> 1) << 6) | lane, bid, mt, nt, M, QQ, ph);
+}
+
+// -------------------------------------------------------------------------------------
 // Ping-pong bf16 gather-GEMM for the large shapes: 256 x BN tile (BN = 256 or 192), 8 waves in two
 // groups of 4 (group g owns pixel rows 128g..128g+127, wave wc of a group owns BN/4 output channels),
 // BK = 64, two LDS stage buffers.  Each K-stage runs as 4 phases (one 32-pixel quarter of the
@@ -3359,6 +3532,43 @@ static int launch_ring(int dtype, GemmParams& p, int nphase, const scd_gemm_phas
     SCD_RETURN_LAUNCH();
 }
 
+// Intra-workgroup split K of the 128 x 128 tile (16-bit types; conv_gemm_kernel's KS, and the ring's on that tile):
+// grids of at most 1.5 tiles per CU with >= 16 K stages
+static int tile128_ksplit(const GemmParams& p, int nphase, const scd_gemm_phase* phases, int tiles) {
+    if (p.head_on) return 1;
+    int kt = 0;
+    for (int i = 0; i < nphase; ++i) kt = std::max(kt, phases[i].ntaps * (p.Ci / 64));
+    return kt >= 16 && 2 * (long)tiles <= 3L * num_cus() ? 2 : 1;
+}
+
+// The ring kernel on the 128 x 128 tile (16-bit types), from the shape alone: what launch_tiled would run on
+// conv_gemm_kernel<T,128,128> with its split K (Co > 64, >= 16 K stages, at most 1.5 tiles per CU; not the heads and
+// residual epilogues, which it does not build) when that grid fills the chip, i.e. >= 256 tiles -- the long-K
+// 8,192-row GEMMs at 512 px (layer4 conv1 / conv2 forward, conv2 and deconv1 input gradients).  Its K split is that
+// kernel's, so the results are too.  The launches without split K (the 1x1 downsample forward: 4 K stages) measured no
+// faster on it and stay on the register-staged kernel.
+// force (scd_conv_gemm_sel): any tile count and either K split.
+static int launch_ring128(int dtype, GemmParams& p, int nphase, const scd_gemm_phase* phases, long /*Mtot*/,
+                          hipStream_t st, bool force = false) {
+    if (dtype != SCD_DT_BF16 || p.Co <= 64 || p.head_on || p.res || p.shuf) return -1;
+    const int ntn = cdiv(p.Co, 128);
+    long tiles = 0;
+    for (int i = 0; i < nphase; ++i) tiles += (long)cdiv((long)p.N * phases[i].Qh * phases[i].Qw, 128) * ntn;
+    if (tiles == 0 || tiles >= (1L << 30)) return -1;
+    const int ks = tile128_ksplit(p, nphase, phases, (int)tiles);
+    if (!force && (tiles < 256 || ks != 2)) return -1;
+    fill_tiles(p, nphase, phases, 128, ntn);
+    if (!fill_ranges(dtype, p, false)) return SCD_ERR_ARG;
+    if (ks == 2) {
+        if (p.bnbwd) hipLaunchKernelGGL((conv_gemm_ring128_kernel<2, true>), dim3(tiles), dim3(512), 0, st, p);
+        else hipLaunchKernelGGL((conv_gemm_ring128_kernel<2>), dim3(tiles), dim3(512), 0, st, p);
+    } else {
+        if (p.bnbwd) hipLaunchKernelGGL((conv_gemm_ring128_kernel<1, true>), dim3(tiles), dim3(512), 0, st, p);
+        else hipLaunchKernelGGL((conv_gemm_ring128_kernel<1>), dim3(tiles), dim3(512), 0, st, p);
+    }
+    SCD_RETURN_LAUNCH();
+}
+
 // Every shape no other family takes: the 128 x 128 tile, 256 x 64 for narrow outputs (Co <= 64), bf16 or fp32.
 static int launch_tiled(int dtype, GemmParams& p, int nphase, const scd_gemm_phase* phases, long /*Mtot*/,
                         hipStream_t st) {
@@ -3369,18 +3579,14 @@ static int launch_tiled(int dtype, GemmParams& p, int nphase, const scd_gemm_pha
     return scd_dispatch_dtype(dtype, [&](auto tag) {
         using T = typename decltype(tag)::type;
         if (narrow) return launch_gemm<T, 256, 64>(p, tiles, st);
-        // intra-workgroup split K (16-bit types): grids of at most 1.5 tiles per CU with >= 16 K stages
-        int ks = 1;
-        if (sizeof(T) == 2 && !p.head_on) {
-            int kt = 0;
-            for (int i = 0; i < nphase; ++i) kt = std::max(kt, phases[i].ntaps * (p.Ci / 64));
-            if (kt >= 16 && 2 * (long)tiles <= 3L * num_cus()) ks = 2;
-        }
-        return launch_gemm<T, 128, 128>(p, tiles, st, ks);
+        return launch_gemm<T, 128, 128>(p, tiles, st, sizeof(T) == 2 ? tile128_ksplit(p, nphase, phases, tiles) : 1);
     });
 }
 
-static int conv_gemm_launch(int dtype, GemmParams& p, int nphase, const scd_gemm_phase* phases, void* stream) {
+// sel (scd_conv_gemm_sel): 0 the register-staged 128 x 128 kernel, 1 the ring on that tile, whatever the tile count;
+// SCD_ERR_ARG where that kernel does not take the call.  -1: the library's choice
+static int conv_gemm_launch(int dtype, GemmParams& p, int nphase, const scd_gemm_phase* phases, void* stream,
+                            int sel = -1) {
     if (nphase < 1 || nphase > SCD_MAX_PHASES) return SCD_ERR_ARG;
     const int BK = dtype == SCD_DT_BF16 ? 64 : 32;
     const int EPC = dtype == SCD_DT_BF16 ? 8 : 4;
@@ -3395,6 +3601,12 @@ static int conv_gemm_launch(int dtype, GemmParams& p, int nphase, const scd_gemm
         Mtot += (long)p.N * phases[i].Qh * phases[i].Qw;
     }
     hipStream_t st = (hipStream_t)stream;
+    if (sel >= 0) {
+        if (dtype != SCD_DT_BF16 || p.Co <= 64 || sel > 1) return SCD_ERR_ARG;
+        const int rs = sel == 1 ? launch_ring128(dtype, p, nphase, phases, Mtot, st, true)
+                                : launch_tiled(dtype, p, nphase, phases, Mtot, st);
+        return rs < 0 ? SCD_ERR_ARG : rs;
+    }
     int rc = launch_stream1x1(dtype, p, nphase, phases, Mtot, st);
     if (rc < 0 && stream1x1_mode() == 2) return SCD_ERR_ARG;
     if (rc < 0) rc = launch_heads384(dtype, p, nphase, phases, Mtot, st);
@@ -3403,6 +3615,7 @@ static int conv_gemm_launch(int dtype, GemmParams& p, int nphase, const scd_gemm
     if (p.bnbwd && dtype != SCD_DT_BF16) return SCD_ERR_ARG;   // BN-backward sums: 16-bit epilogues (caller falls back)
     rc = launch_l1p(dtype, p, nphase, phases, Mtot, st);
     if (rc < 0) rc = launch_ring(dtype, p, nphase, phases, Mtot, st);
+    if (rc < 0) rc = launch_ring128(dtype, p, nphase, phases, Mtot, st);
     if (rc < 0) rc = launch_tiled(dtype, p, nphase, phases, Mtot, st);
     return rc;
 }
@@ -3433,6 +3646,27 @@ extern "C" int scd_conv_gemm(int dtype, const void* x, const void* w, void* y, c
     GemmParams p;
     fill_params(p, x, w, y, bias, stats, N, Hi, Wi, Ci, Ho, Wo, Co, in_stride, out_stride, wrow, relu, accumulate);
     return conv_gemm_launch(dtype, p, nphase, phases, stream);
+}
+
+// scd_conv_gemm, or scd_conv_gemm_bnbwd when bn_y is given (stats is then that call's bn_stats), on the kernel named by
+// `kernel` (0: conv_gemm_kernel<T,128,128>, 1: conv_gemm_ring128_kernel) whatever the tile count: the tests run both
+// on one input.  16-bit types and Co > 64 only.
+extern "C" int scd_conv_gemm_sel(int dtype, int kernel, const void* x, const void* w, void* y, const float* bias,
+                                 double* stats, int N, int Hi, int Wi, int Ci, int Ho, int Wo, int Co, int in_stride,
+                                 int out_stride, int wrow, int relu, int accumulate, int nphase,
+                                 const scd_gemm_phase* phases, const void* bn_y, const float* mean,
+                                 const float* invstd, const float* relu_scale, const float* relu_shift, void* stream) {
+    SCD_F16_FWD(scd_conv_gemm_sel, kernel, x, w, y, bias, stats, N, Hi, Wi, Ci, Ho, Wo, Co, in_stride, out_stride, wrow,
+                relu, accumulate, nphase, phases, bn_y, mean, invstd, relu_scale, relu_shift, stream);
+    if (kernel < 0 || kernel > 1) return SCD_ERR_ARG;
+    GemmParams p;
+    fill_params(p, x, w, y, bias, stats, N, Hi, Wi, Ci, Ho, Wo, Co, in_stride, out_stride, wrow, relu, accumulate);
+    if (bn_y) {
+        if (!mean || !invstd || !relu_scale || !relu_shift || !stats || bias || relu || accumulate) return SCD_ERR_ARG;
+        p.bnbwd = 1;
+        p.bny = (const char*)bn_y; p.bn_mean = mean; p.bn_invstd = invstd; p.bn_rsc = relu_scale; p.bn_rsh = relu_shift;
+    }
+    return conv_gemm_launch(dtype, p, nphase, phases, stream, kernel);
 }
 
 // y = act(acc + bias + res): the folded-BatchNorm inference conv (scdhip/infer.py).  The residual joins the unrounded

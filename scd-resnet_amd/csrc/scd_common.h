@@ -21,6 +21,7 @@
 // to it)
 #define SCD_F16_ENTRY_POINTS(X) \
     X(scd_conv_gemm) \
+    X(scd_conv_gemm_sel) \
     X(scd_conv_gemm_bnbwd) \
     X(scd_conv_gemm_res) \
     X(scd_conv_gemm_heads) \

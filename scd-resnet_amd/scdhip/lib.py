@@ -64,6 +64,8 @@ LP = ctypes.POINTER(c_long)
 # name -> (restype, argtypes); mirrors include/scdhip.h one to one
 SIGNATURES = {
     "scd_conv_gemm": (I, [I, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, I, ctypes.POINTER(GemmPhase), P]),
+    "scd_conv_gemm_sel": (I, [I, I, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, I, ctypes.POINTER(GemmPhase), P, P,
+                              P, P, P, P]),
     "scd_conv_gemm_res": (I, [I, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, ctypes.POINTER(GemmPhase), P]),
     "scd_conv_gemm_heads": (I, [I, P, P, P, P, I, I, I, I, I, IP, PP, PP, PP, P]),
     "scd_conv_gemm_heads_keep": (I, [I, P, P, P, P, I, I, I, I, I, IP, PP, PP, PP, P, I, P]),

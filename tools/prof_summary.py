@@ -43,6 +43,9 @@ def short(name):
     if m:
         return "conv_gemm_ring_kernel<%s,256,128%s%s>" % (half, ",heads" if m.group(1) == "true" else "",
                                                           ",bnbwd" if m.group(3) == "true" else "")
+    m = re.search(r"conv_gemm_ring128_kernel<(\d)(, (true|false))?>", n)
+    if m:
+        return "conv_gemm_ring128_kernel<%s,128,128,ks%s%s>" % (half, m.group(1), ",bnbwd" if m.group(3) == "true" else "")
     m = re.search(r"conv_gemm_pp_kernel<(\d+), (true|false)>", n)
     if m:
         return "conv_gemm_pp_kernel<%s,256,%s%s>" % (half, m.group(1), ",heads" if m.group(2) == "true" else "")
