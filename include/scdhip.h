@@ -593,6 +593,19 @@ int scd_adam_step_dev(float* p, const float* g, float* m, float* v, long n, doub
 int scd_sgd_step_dev(float* p, const float* g, float* buf, long n, double* hyper, float momentum, float dampening,
                      float weight_decay, int nesterov, float gscale,
                      const unsigned long long* skip, void* stream);
+/* ---- gradient guard of the dynamic fp16 loss scale (scdhip/amp.py): one pass over the flat fp32 gradient g[n],
+ * queued right before the optimizer kernel.  Every output is overwritten by every call:
+ *   verdict[1] = the number of non-finite elements (exponent bits all ones: +-inf and every NaN pattern);
+ *   verdict[0] = the optimizer's skip word: non-zero iff verdict[1] != 0 or (also != NULL and *also != 0) -- `also`
+ *                is how the peer-memory SyncBN error word stays in force behind the one skip pointer;
+ *   *sumsq     = the fp64 sum of (double)g[i]*g[i] over the finite elements (each square exact in fp64).
+ * Deterministic: per-workgroup fp64 partials in ws, added in an order fixed by the workgroup index.  No host
+ * synchronisation, no allocation, no state in the library: ws (scd_grad_guard_workspace(n) bytes, device) must be zero
+ * at the first call and is left zero.  n == 0 is valid (count 0, sum 0, verdict[0] follows `also`).  SCD_ERR_ARG for
+ * n < 0, g NULL with n > 0, ws / verdict / sumsq NULL, or g not 16-byte aligned. */
+size_t scd_grad_guard_workspace(long n);
+int scd_grad_guard(const float* g, long n, const unsigned long long* also, void* ws, unsigned long long* verdict,
+                   double* sumsq, void* stream);
 
 /* ---- corner pooling (cornerPooling/source/{top,bottom,left,right}Pool.cpp) ----
  * dir: 0 top (max over k>=h), 1 bottom (k<=h), 2 left (k>=w), 3 right (k<=w); NHWC dtype.

@@ -2,7 +2,7 @@
 
 Same default keys and the same overlay rule: a JSON config replaces only keys that already
 exist (configuration.py:150-153); string values may reference other keys as `{key}` format
-fields.  Six keys are added: ``computeDtype`` ("bf16" | "fp16" | "fp32"), the MFMA precision of the
+fields.  Seven keys are added: ``computeDtype`` ("bf16" | "fp16" | "fp32"), the MFMA precision of the
 HIP path (the reference trains in fp32 without AMP), ``stepGraph`` (true | false, default false):
 replay the training step as a captured HIP graph after two eager steps (single-process runs;
 scdhip/graph.py -- measured slower than eager issue on ROCm 7), ``rotateAugmentation``
@@ -15,7 +15,10 @@ labels) to the device at the first training batch and build every batch there fr
 training batches and validation set alike, the corner maps rendered by scd_render_corner_targets, and
 ``cornerEmbeddings`` (true | false, default false; needs cornerTargets): the corner layout grows to [heat, mask, regr,
 tl, br, tl_inds, br_inds, valid], the cells and slots cornerNetAE's embedding loss gathers its tags at
-(scd_corner_tag_inds); `syntheticCorner` reads it too.
+(scd_corner_tag_inds); `syntheticCorner` reads it too, and ``lossScale`` ("static" | "dynamic",
+default "static"; "dynamic" needs computeDtype "fp16" and no stepGraph): with "dynamic" the fp16 loss scale follows
+torch.amp.GradScaler's rule -- a step whose flat gradient holds an inf or NaN is skipped on the device and the scale
+backs off, and it grows again after a run of clean steps (scdhip/amp.py).
 """
 import os
 
@@ -57,6 +60,7 @@ class Configuration:
         c["residentDataset"] = False
         c["cornerTargets"] = False
         c["cornerEmbeddings"] = False
+        c["lossScale"] = "static"
         self.config = c
 
     # -- formatted / plain accessors (configuration.py:46-146)
@@ -99,6 +103,7 @@ class Configuration:
     residentDataset = property(lambda s: bool(s.config["residentDataset"]))
     cornerTargets = property(lambda s: bool(s.config["cornerTargets"]))
     cornerEmbeddings = property(lambda s: bool(s.config["cornerEmbeddings"]))
+    lossScale = property(lambda s: s.config["lossScale"])
 
     def useGPU(self):
         # a bound method, hence always truthy when tested without a call (reference quirk)

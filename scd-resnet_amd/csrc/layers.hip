@@ -816,7 +816,109 @@ __global__ void sgd_dev_kernel(float* p, const float* g, float* buf, long n, con
         p[i] = pi - lr * d;
     }
 }
+
+// ---------------------------------------------------------------- gradient guard (dynamic fp16 loss scaling)
+// One read of the flat fp32 gradient right before the optimizer kernel: the count of non-finite elements (exponent
+// bits all ones) and the fp64 sum of squares of the finite ones.  Each workgroup leaves one fp64 partial and one count
+// in ws; the finalize launch adds them in an order fixed by the workgroup index alone (each lane its run of
+// consecutive partials, then the wave tree), so equal input gives equal bits, writes {skip word, count} and the sum
+// with vector stores, and zeroes ws again.
+constexpr int GUARD_MAX_PARTS = 1024;      // workgroups of the pass = partials in ws (4 per CU on a 256-CU chip)
+constexpr int GUARD_UNROLL = 4;            // 16-byte loads in flight per thread: 16 KiB per workgroup
+
+__device__ __forceinline__ void guard_take(float x, double& s, unsigned long long& c) {
+    const bool bad = (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u;
+    const double d = bad ? 0.0 : (double)x;
+    s += d * d;                            // 24-bit significands: the square is exact in fp64
+    c += bad ? 1ull : 0ull;
+}
+
+__device__ __forceinline__ void guard_take4(const float4& v, double& s, unsigned long long& c) {
+    guard_take(v.x, s, c);
+    guard_take(v.y, s, c);
+    guard_take(v.z, s, c);
+    guard_take(v.w, s, c);
+}
+
+__global__ __launch_bounds__(256) void grad_guard_kernel(const float* __restrict__ g, long n, double* psum,
+                                                         unsigned long long* pcnt) {
+    __shared__ double ls[4];
+    __shared__ unsigned long long lc[4];
+    const float4* g4 = (const float4*)g;
+    const long nv = n >> 2;
+    const long stride = (long)gridDim.x * 256;
+    double s = 0.0;
+    unsigned long long c = 0;
+    long i = blockIdx.x * 256L + threadIdx.x;
+    for (; i + (GUARD_UNROLL - 1) * stride < nv; i += GUARD_UNROLL * stride) {
+        float4 v[GUARD_UNROLL];
+#pragma unroll
+        for (int u = 0; u < GUARD_UNROLL; ++u) v[u] = g4[i + u * stride];
+#pragma unroll
+        for (int u = 0; u < GUARD_UNROLL; ++u) guard_take4(v[u], s, c);
+    }
+    for (; i < nv; i += stride) guard_take4(g4[i], s, c);
+    // the n % 4 elements behind the last whole vector
+    if (blockIdx.x == 0 && (nv << 2) + threadIdx.x < n) guard_take(g[(nv << 2) + threadIdx.x], s, c);
+    s = wave_sum_d(s);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+    if ((threadIdx.x & 63) == 0) {
+        ls[threadIdx.x >> 6] = s;
+        lc[threadIdx.x >> 6] = c;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        psum[blockIdx.x] = (ls[0] + ls[1]) + (ls[2] + ls[3]);
+        pcnt[blockIdx.x] = lc[0] + lc[1] + lc[2] + lc[3];
+    }
+}
+
+__global__ __launch_bounds__(64) void grad_guard_final_kernel(double* psum, unsigned long long* pcnt, int nparts,
+                                                              const unsigned long long* also,
+                                                              unsigned long long* verdict, double* sumsq) {
+    const int per = (nparts + 63) / 64;
+    const int lo = threadIdx.x * per, hi = min(nparts, lo + per);
+    double s = 0.0;
+    unsigned long long c = 0;
+    for (int i = lo; i < hi; ++i) {
+        s += psum[i];
+        c += pcnt[i];
+        psum[i] = 0.0;
+        pcnt[i] = 0;
+    }
+    s = wave_sum_d(s);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+    if (threadIdx.x == 0) {
+        verdict[0] = c | (also ? *also : 0ull);
+        verdict[1] = c;
+        *sumsq = s;
+    }
+}
 }  // namespace
+
+extern "C" size_t scd_grad_guard_workspace(long n) {
+    (void)n;                               // one partial and one count per workgroup, whatever the length
+    return (size_t)GUARD_MAX_PARTS * (sizeof(double) + sizeof(unsigned long long));
+}
+
+extern "C" int scd_grad_guard(const float* g, long n, const unsigned long long* also, void* ws,
+                              unsigned long long* verdict, double* sumsq, void* stream) {
+    if (n < 0 || (n > 0 && !g) || !ws || !verdict || !sumsq || ((uintptr_t)g & 15)) return SCD_ERR_ARG;
+    double* psum = (double*)ws;
+    unsigned long long* pcnt = (unsigned long long*)(psum + GUARD_MAX_PARTS);
+    int parts = 0;
+    if (n > 0) {
+        static const int resident = resident_grid((const void*)grad_guard_kernel, 256);
+        const long want = std::max<long>(1, ((n >> 2) + 255) / 256);
+        parts = (int)std::min<long>(want, std::min(resident, GUARD_MAX_PARTS));
+        hipLaunchKernelGGL(grad_guard_kernel, dim3(parts), dim3(256), 0, (hipStream_t)stream, g, n, psum, pcnt);
+    }
+    hipLaunchKernelGGL(grad_guard_final_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, psum, pcnt, parts, also,
+                       verdict, sumsq);
+    SCD_RETURN_LAUNCH();
+}
 
 extern "C" size_t scd_heads_bwd_accsize(int nh, int Hd, const int* od) {
     int nout = 0;

@@ -14,6 +14,8 @@ execution side:
   * batches are moved to this rank's device (the reference datasets pin cuda:0);
   * with ``stepGraph`` (opt-in) a single-process run replays the step as a captured HIP graph after two
     eager steps (scdhip.graph.StepGraph: same kernels, one hipGraphLaunch per step);
+  * with ``lossScale`` "dynamic" (opt-in, fp16 only, no stepGraph) a scdhip.amp.DynamicLossScale is attached to the
+    optimizer: overflowed steps are skipped on the device and the loss scale follows torch.amp.GradScaler's rule;
   * resume loads after the wrap and uses learningRateDecayRate[index] (fixes the reference's
     `module.` prefix mismatch and [t] index, networkFactory.py:116-124).
 The CPU path (no -gpu) is not part of this framework: the CPU restatement is oracle/.
@@ -33,6 +35,7 @@ from tqdm import tqdm
 from configuration import defaultConfig
 from logger import Logger, monitorStdOutStream
 from scdhip import ops
+from scdhip.amp import DynamicLossScale
 from scdhip.flat import FlatAdam, FlatDDP, FlatSGD
 from scdhip.graph import StepGraph
 from scdhip.loss import mean_backward
@@ -93,6 +96,15 @@ class NetworkFactory(object):
         if not useGPU:
             raise RuntimeError("scd-resnet_amd trains on MI355X only (run train.py with -gpu); the CPU "
                                "restatement of the reference lives in oracle/ and is test infrastructure")
+        if defaultConfig.lossScale not in ("static", "dynamic"):
+            raise ValueError("lossScale must be 'static' or 'dynamic', got {!r}".format(defaultConfig.lossScale))
+        if defaultConfig.lossScale == "dynamic":
+            if _DTYPES.get(defaultConfig.computeDtype) is not torch.float16:
+                raise ValueError("lossScale 'dynamic' needs computeDtype 'fp16' (got {!r}): nothing is scaled in "
+                                 "bf16 or fp32".format(defaultConfig.computeDtype))
+            if defaultConfig.stepGraph:
+                raise ValueError("lossScale 'dynamic' does not run with stepGraph: a captured step bakes the scale "
+                                 "into its launches, and re-capture on a scale change is not implemented")
 
         modelPy = defaultConfig.dirModel
         Logger.info("Loaded Model From: {}".format(modelPy))
@@ -126,6 +138,10 @@ class NetworkFactory(object):
             Logger.err(":: networkFactory.py :: Unknown Optimizer '{}', Currently Support 'sgd' or 'adam'".format(
                 defaultConfig.optimizer))
             sys.exit()
+        self.lossScaler = None
+        if defaultConfig.lossScale == "dynamic":
+            self.lossScaler = DynamicLossScale().attach(self.optimizer)
+            self.lossScaler.on_change = self._logLossScale
         self.device = None
         self.stepGraph = None
 
@@ -196,6 +212,8 @@ class NetworkFactory(object):
                         it += 1
                         loss, lossStatsT = self.train(**data)
                         lossv = loss.item()
+                        if self.lossScaler is not None:
+                            self.lossScaler.update()        # loss.item() has synchronised: this step's verdict is in
                         pbar.set_description("Loss:" + format(lossv, "-10.4f"))
                         lossSave += [it, lossv]
                         lossSave += [x.item() for x in lossStatsT]
@@ -214,6 +232,8 @@ class NetworkFactory(object):
                             Logger.info(evalr)
 
                         if it % defaultConfig.snapshotFrequency == 0:
+                            if self.lossScaler is not None:
+                                self.lossScaler.update(block=True)
                             self.saveParameters()
                             numpyLoss = numpy.array(lossSave)
                             dim = 2 + len(lossStatsT)
@@ -234,6 +254,8 @@ class NetworkFactory(object):
                             finished = True
                             break
 
+        if self.lossScaler is not None:
+            self.lossScaler.update(block=True)
         with open(defaultConfig.dirResult + "evals.{}.txt".format(defaultConfig.trainName), "w") as evalText:
             evalText.writelines(evalResult)
 
@@ -278,6 +300,10 @@ class NetworkFactory(object):
         Logger.warn(":: networkFactory.py :: Setting Learning Rate to: {}".format(lr))
         for group in self.optimizer.param_groups:
             group["lr"] = lr
+
+    def _logLossScale(self, old, new, nonfinite):
+        Logger.warn(":: networkFactory.py :: Iteration {}: Loss Scale {:g} -> {:g} ({} Non-Finite Gradient Elements)"
+                    .format(defaultConfig.currentIteration + 1, old, new, nonfinite))
 
     def _load_into_wrapped(self, params):
         keys = list(params.keys())

@@ -99,6 +99,7 @@ class _FlatOptimizer(torch.optim.Optimizer):
         self._step = 0          # host mirror of the device step counter (state_dict)
         self._hyper = None      # device {lr, step} fp64
         self._dev_lr = None     # the lr last written to _hyper
+        self._scaler = None     # scdhip.amp.DynamicLossScale, when one is attached
 
     def _all_params(self):
         return [p for g in self.param_groups for p in g["params"]]
@@ -146,7 +147,29 @@ class _FlatOptimizer(torch.optim.Optimizer):
         self._step += 1
         return fp, self.param_groups[0]
 
+    def _attach_scaler(self, scaler):
+        if scaler is not None and self._scaler is not None:
+            raise RuntimeError("this optimizer already has a DynamicLossScale attached")
+        self._scaler = scaler
+
+    def _skip_word(self, fp):
+        """The device word the step kernels test: ops.optimizer_skip_word(), or with a DynamicLossScale attached the
+        verdict of the gradient guard it queues here (that word OR-ed in), right before the optimizer kernel."""
+        from . import ops
+        skip = ops.optimizer_skip_word()
+        return skip if self._scaler is None else self._scaler.guard(fp.grad, also=skip)
+
+    def _with_scaler(self, sd):
+        if self._scaler is not None:
+            self._scaler.update(block=True)         # skipped steps come off the mirror before it is saved
+            sd = dict(sd, step=self._step, loss_scale=self._scaler.state_dict())
+        return sd
+
     def _load_common(self, sd):
+        if self._scaler is not None:
+            self._scaler.update(block=True)
+            if "loss_scale" in sd:
+                self._scaler.load_state_dict(sd["loss_scale"])
         self._step = sd["step"]
         for g, s in zip(self.param_groups, sd["param_groups"]):
             g.update(s)
@@ -177,13 +200,13 @@ class FlatAdam(_FlatOptimizer):
         from . import ops
         fp, g = self._begin_step()
         ops.adam_step_dev(fp.data, fp.grad, self._m, self._v, self._hyper, g["betas"][0], g["betas"][1], g["eps"],
-                          gscale=fp.grad_scale, skip=ops.optimizer_skip_word())
+                          gscale=fp.grad_scale, skip=self._skip_word(fp))
         return None
 
     def state_dict(self):
-        return {"step": self._step, "param_groups": self._groups_sd(),
-                "exp_avg": None if self._m is None else self._m.cpu(),
-                "exp_avg_sq": None if self._v is None else self._v.cpu()}
+        return self._with_scaler({"step": self._step, "param_groups": self._groups_sd(),
+                                  "exp_avg": None if self._m is None else self._m.cpu(),
+                                  "exp_avg_sq": None if self._v is None else self._v.cpu()})
 
     def load_state_dict(self, sd):
         self._load_common(sd)
@@ -217,15 +240,15 @@ class FlatSGD(_FlatOptimizer):
         from . import ops
         fp, g = self._begin_step()
         ops.sgd_step_dev(fp.data, fp.grad, self._buf, self._hyper, g["momentum"], g["dampening"], g["weight_decay"],
-                         g["nesterov"], gscale=fp.grad_scale, skip=ops.optimizer_skip_word())
+                         g["nesterov"], gscale=fp.grad_scale, skip=self._skip_word(fp))
         return None
 
     def state_dict(self):
         # torch emits a momentum_buffer only once a step has created it: the flat buffer exists from flat() on, so the
         # device flag hyper[2] (set by the first step or a loaded buffer) says whether it is one yet
         init = self._buf is not None and self._hyper is not None and float(self._hyper[2].item()) != 0.0
-        return {"step": self._step, "param_groups": self._groups_sd(),
-                "momentum_buffer": self._buf.cpu() if init else None}
+        return self._with_scaler({"step": self._step, "param_groups": self._groups_sd(),
+                                  "momentum_buffer": self._buf.cpu() if init else None})
 
     def load_state_dict(self, sd):
         buf = sd.get("momentum_buffer")

@@ -144,6 +144,8 @@ SIGNATURES = {
     "scd_adam_step": (I, [P, P, P, P, L, F, F, F, F, F, F, F, P]),
     "scd_adam_step_dev": (I, [P, P, P, P, L, P, F, F, F, F, P, P]),
     "scd_sgd_step_dev": (I, [P, P, P, L, P, F, F, F, I, F, P, P]),
+    "scd_grad_guard_workspace": (c_size_t, [L]),
+    "scd_grad_guard": (I, [P, L, P, P, P, P, P]),
     "scd_render_center_targets": (I, [P, P, I, I, I, F, P, P, P, P, P]),
     "scd_render_corner_targets": (I, [P, P, I, I, I, F, P, P, P, P, P, P, P]),
     "scd_render_corner_targets_split": (I, [P, P, I, I, I, F, P, P, P, P, P, P, I, P]),

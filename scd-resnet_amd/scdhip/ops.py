@@ -34,6 +34,17 @@ def loss_scale(dtype):
     return LossScale.f16 if dtype == torch.float16 else 1.0
 
 
+def set_loss_scale(S):
+    """Set the fp16 loss scale (a power of two, so 1/S stays an exact unscale) and return the one it replaces: how
+    scdhip.amp.DynamicLossScale moves it between steps.  A backward pass reads it when it runs, so change it between
+    steps only; a captured step graph has it baked into its launches."""
+    S = float(S)
+    if not (S > 0.0 and math.isfinite(S) and math.frexp(S)[0] == 0.5):
+        raise ValueError("set_loss_scale: %r is not a positive power of two" % (S,))
+    old, LossScale.f16 = LossScale.f16, S
+    return old
+
+
 def begin_loss_scale(dtype):
     """Called where a backward pass enters the fp16 path (HeadsFn.backward): returns the factor to multiply the
     incoming gradients by and marks the running backward pass as scaled."""
@@ -1582,6 +1593,24 @@ def optimizer_skip_word():
     that path is on -- a failed call NaN-poisons its statistics, so that step's gradients must not reach the weights
     -- else None (no test)."""
     return _BNSync.peer.err if _BNSync.peer is not None else None
+
+
+def grad_guard_workspace(n):
+    """Bytes of zeroed device workspace scd_grad_guard needs for an n-element gradient."""
+    return int(L.lib().scd_grad_guard_workspace(int(n)))
+
+
+def grad_guard(g, ws, verdict, sumsq, also=None):
+    """One pass over the flat fp32 gradient g (scd_grad_guard): verdict = {skip word, non-finite count} (device
+    int64[2]), sumsq = the fp64 sum of squares of the finite elements (device, 8 bytes); also: a further device skip
+    word OR-ed into verdict[0] (optimizer_skip_word()).  ws: grad_guard_workspace bytes, zero at first use."""
+    _need_gpu(g, ws, verdict, sumsq, also)
+    if g.dtype != torch.float32 or not g.is_contiguous():
+        raise RuntimeError("grad_guard: the gradient must be a contiguous fp32 tensor")
+    if ws.numel() * ws.element_size() < grad_guard_workspace(g.numel()) or verdict.numel() * verdict.element_size() < 16:
+        raise RuntimeError("grad_guard: workspace or verdict buffer too small")
+    L.call("scd_grad_guard", ptr(g), g.numel(), ptr(also) if also is not None else None, ptr(ws), ptr(verdict),
+           ptr(sumsq), stream())
 
 
 def adam_step_dev(p, g, m, v, hyper, beta1, beta2, eps, gscale=1.0, skip=None):
