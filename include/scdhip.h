@@ -161,6 +161,27 @@ int scd_pad_channels(int dtype, const void* src, long rows, int C, int Cp, void*
 int scd_upsample2x_add(int dtype, const void* up, const void* low, void* out, int N, int h, int w, int C, void* stream);
 int scd_upsample2x_add_bwd(int dtype, const void* dout, void* dlow, int N, int h, int w, int C, void* stream);
 
+/* Modulated deformable convolution (DCNv2, models/backbones/deformable/ of the reference): the sampling half, NHWC.
+ * 3x3 taps k = 3i + j, stride 1, pad 1, dilation 1, G deformable groups of C/G channels.  x is (N,H,W,C); om is
+ * (N,H,W,P), P >= 27G: channel 18g + 2k is tap k's row offset dh, 18g + 2k + 1 its column offset dw, 18G + 9g + k its
+ * mask m (sigmoid = 0) or the mask's logit (sigmoid = 1); channels >= 27G are padding and never read.  The sample
+ * point of output pixel (h, w) is (h - 1 + i + dh, w - 1 + j + dw); a bilinear corner outside [0,H-1] x [0,W-1]
+ * contributes 0.
+ *   scd_dcn_cols      cols[pix][k*C + c] = m * sum_corners weight * x[corner][c], the blend in fp32, one rounding.
+ *                     cols is (N*H*W, 9C) in dtype: the K order of pack mode 0 of the (Co,C,3,3) weight, so the
+ *                     convolution is the 1x1 gather-GEMM over cols with Ci = 9C.
+ *   scd_dcn_cols_bwd  dom (N,H,W,P) is written: d dh, d dw = m * sum_c dcol_c * sum_corners (d weight / d h, w) * x,
+ *                     d mask = sum_c dcol_c * val_c (times sigmoid'(logit) when sigmoid = 1), pad channels 0; the
+ *                     channel sums run in a fixed order, so dom is bit-identical from call to call.
+ *                     dx32 (N,H,W,C) fp32 is added into (the caller zeroes it): dcol * m * weight at every corner
+ *                     whose weight is not 0, with float atomics -- its last bits depend on their arrival order.
+ * SCD_ERR_ARG before any launch: C/G not a multiple of 8 (16-bit types) / 4 (fp32), P < 27G or not such a multiple,
+ * an extent <= 0, sigmoid not 0 or 1, cols or dom or dx32 sharing a byte with an input (or with each other). */
+int scd_dcn_cols(int dtype, const void* x, const void* om, void* cols, int N, int H, int W, int C, int G, int P,
+                 int sigmoid, void* stream);
+int scd_dcn_cols_bwd(int dtype, const void* dcols, const void* x, const void* om, float* dx32, void* dom, int N, int H,
+                     int W, int C, int G, int P, int sigmoid, void* stream);
+
 /* Batched weight packing: all operand layouts of one training step in one launch.  descs (device memory)
  * are sorted by start; descriptor d covers elements [start, start + count) of the concatenated index space:
  * mode 0: out[row_off + a][t*B + b] = w[a][b][t], count = A * ldp (k >= T*B zero-filled);

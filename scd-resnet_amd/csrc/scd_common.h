@@ -5,7 +5,7 @@
 #include <string.h>
 
 // fp16 compute mode (SCD_DT_F16).  The type-generic sources (the Makefile's F16SRCS: conv_gemm, bn, layers, stem, pad,
-// upsample) are compiled twice:
+// upsample, deform) are compiled twice:
 // once as written (16-bit storage type h16 = __bf16, v_mfma_f32_16x16x32_bf16) and once with SCD_F16_BUILD, where h16
 // is _Float16, the MFMA is v_mfma_f32_16x16x32_f16 and every entry point on the list below gets the symbol name
 // name__f16.  Those sources name the 16-bit type h16 (and h16x8 / mfma_16x16x32_h16) wherever it is the build's type;
@@ -53,7 +53,9 @@
     X(scd_stem_bwd_combine) \
     X(scd_pad_channels) \
     X(scd_upsample2x_add) \
-    X(scd_upsample2x_add_bwd)
+    X(scd_upsample2x_add_bwd) \
+    X(scd_dcn_cols) \
+    X(scd_dcn_cols_bwd)
 #ifdef SCD_F16_BUILD
 // (the preprocessor cannot write a #define per list item: the second build's definitions, and its calls from one
 // listed entry point to another, get their symbol name from this redeclaration)

@@ -12,6 +12,7 @@ import sys
 import torch
 
 from logger import Logger
+from models.backbones.deformable import DCN
 from models.backbones.terminal import BackboneTerminal
 from models.backbones.utility import convolution3x3
 from scdhip import blocks, ops
@@ -118,15 +119,20 @@ def _is_corner_head(m):
 class ResNet(torch.nn.Module):
     """ResNet(inputDimension, block, layers, preprocess, terminals, decoder, dimensions) -- residuals.py:184-353.
 
+    ``deformable=True`` (not in the reference, which wires its DCN into no model) builds the ResNet-DCN family: a new
+    ``deformLayers`` ModuleList of Sequential(DCN, BatchNorm2d, ReLU), one per up-sampling stage, run before that
+    stage's deconv.  Off, no module, state-dict key or launch differs.
+
     ``compute_dtype`` (torch.bfloat16 default, torch.float16 with a static loss scale, torch.float32 for parity)
     selects the MFMA
     path: bf16 v_mfma_f32_16x16x32_bf16 or exact-f32 v_mfma_f32_16x16x4_f32.
     """
 
     def __init__(self, inputDimension, block, layers, preprocess=None, terminals=[], decoder=None,
-                 dimensions=[64, 64, 128, 256, 512, 256, 256, 256], **kwargs):
+                 dimensions=[64, 64, 128, 256, 512, 256, 256, 256], deformable=False, **kwargs):
         self.inputDimension = dimensions[0]
         self.deconvolutionWithBias = False
+        self.deformable = bool(deformable)
         self.terminals = {}
         self.decoder = decoder
         super(ResNet, self).__init__()
@@ -187,9 +193,19 @@ class ResNet(torch.nn.Module):
             Logger.err(":: residuals.py :: Inconsistant Number of Layers. ")
             sys.exit()
         numLayers = []
+        if self.deformable:
+            # ResNet-DCN: a 3x3 modulated deformable conv + BN + ReLU in front of each up-sampling stage, which then
+            # reads `dimension` channels.  A list of its own: deconvolutionLayers keeps its [deconv, BN, ReLU] x n shape
+            self.deformLayers = torch.nn.ModuleList()
         for i in range(nLayers):
             kernel, padding, outputPadding = self.getDeconvConfig(kernels[i], i)
             dimension = dimensions[i]
+            if self.deformable:
+                self.deformLayers.append(torch.nn.Sequential(
+                    DCN(self.inputDimension, dimension, 3, 1, 1),
+                    torch.nn.BatchNorm2d(dimension, momentum=BNMOMENTUM),
+                    torch.nn.ReLU(inplace=True)))
+                self.inputDimension = dimension
             numLayers.append(torch.nn.ConvTranspose2d(
                 in_channels=self.inputDimension, out_channels=dimension, kernel_size=kernel, stride=2,
                 padding=padding, output_padding=outputPadding, bias=self.deconvolutionWithBias))
@@ -217,6 +233,9 @@ class ResNet(torch.nn.Module):
             dc, dbn = dl[i], dl[i + 1]
             if dc.bias is not None or dc.output_padding != (0, 0):
                 raise NotImplementedError("deconv with bias/output_padding")
+            if getattr(self, "deformable", False):
+                dcn, dcbn = self.deformLayers[i // 3][0], self.deformLayers[i // 3][1]
+                h = blocks.DeformConvFn.apply(h, dcn.weight, dcn, dcbn, True)
             h = blocks.DeconvBNFn.apply(h, dc.weight, dc, dbn)
         return h
 

@@ -51,14 +51,15 @@ resnetHeatmapTerminal, resnetSizeTerminal, resnetOffsetTerminal = make_terminals
 
 
 class CenterNetResidual(ResNet):
-    """CenterNetResidual(numLayers, dims) -- centerNetOffset.py:150-168."""
+    """CenterNetResidual(numLayers, dims) -- centerNetOffset.py:150-168.  deformable=True: the ResNet-DCN variant
+    (models/backbones/residuals.ResNet)."""
 
     HEAD_DIM = 128
 
-    def __init__(self, numLayers, dims=[64, 64, 128, 256, 512, 256, 256, 256]):
+    def __init__(self, numLayers, dims=[64, 64, 128, 256, 512, 256, 256, 256], deformable=False):
         blockType, layers = ResNetSpec[numLayers]
         super(CenterNetResidual, self).__init__(1, blockType, layers, terminals=make_terminals(self.HEAD_DIM),
-                                                decoder=decodeCenterNet, dimensions=dims)
+                                                decoder=decodeCenterNet, dimensions=dims, deformable=deformable)
         self.initialize(numLayers)
 
 

@@ -8,6 +8,8 @@ Each Function runs one reference module group entirely on libscdhip kernels:
   UpsampleAddFn Upsample(2, nearest) + MergeUp of an hourglass level       hourglass.py:113-114
   DeconvBNFn    ConvTranspose2d(k4,s2,p1,no bias)+BN+ReLU                 residuals.py:286-310
   ConvBNFn      Convolution (conv+BN+ReLU) / conv+BN                      convolutions.py:25-49
+  DeformConvFn  DCN: offset conv, sampled columns, 1x1 GEMM [+BN [+ReLU]]  deformable/dcn_v2.py:146-191
+  DeformConvV2Fn  dcn_v2_conv with offset and mask as inputs               deformable/dcn_v2.py:14-92
   HeadsFn       all CenterNet terminals fused: one 3x3 GEMM with N = sum of
                 hidden widths (+bias+ReLU epilogue) and the per-head 1x1s  centerNetOffset.py:103-122
 
@@ -310,6 +312,96 @@ class ConvBNFn(torch.autograd.Function):
         dx = ops.conv_dgrad(dy, ops.pack_weight(w, x.dtype, 1), x.shape[3], x.shape[1], x.shape[2], kh, kw, s, p)
         grads_ready(conv, bn)
         return dx, None, None, None, None
+
+
+def _dcn_conv_fwd(x, om, G, sigmoid, w, bias, stats=None):
+    """The deformable conv proper: sampled columns (N,H,W,9C), then the 1x1 GEMM over them with w's pack mode 0."""
+    cols = ops.dcn_cols(x, om, G, sigmoid)
+    y = ops.conv_fwd(cols, ops.pack_weight(w, x.dtype, 0), w.shape[0], 1, 1, 1, 0, bias=bias, stats=stats)
+    return cols, y
+
+
+def _dcn_cols_grad(dy, w):
+    """Gradient towards the columns: a 1x1 GEMM with the transposed weight, rows tap-major (pack mode 2)."""
+    return ops.conv_fwd(dy, ops.pack_concat([w], dy.dtype, 2), 9 * w.shape[1], 1, 1, 1, 0)
+
+
+class DeformConvFn(torch.autograd.Function):
+    """DCN (models/backbones/deformable/dcn_v2.py:146-191 of the reference): offsets and mask logits from the module's
+    own conv_offset_mask, the modulated deformable 3x3 conv with bias, then optionally BatchNorm2d [+ ReLU]."""
+
+    @staticmethod
+    def forward(ctx, x, w, dcn, bn, relu):
+        ops._need_gpu(x, w)
+        G, com = dcn.deformable_groups, dcn.conv_offset_mask
+        P = ops.dcn_om_channels(G, x.dtype)
+        wo, bo = ops.dcn_offset_rows(com.weight, com.bias, P)
+        om = ops.conv_fwd(x, ops.pack_weight(wo, x.dtype, 0), P, 3, 3, 1, 1, bias=bo)
+        Co = dcn.weight.shape[0]
+        training = bn is not None and bn.training
+        stats = ops.bn_stats(bn, "fwd") if training else None
+        cols, y = _dcn_conv_fwd(x, om, G, True, dcn.weight, dcn.bias, stats)
+        if bn is None:
+            out, st = y, None
+        else:
+            st = ops.bn_finalize(bn, stats, Co, y.numel() // Co, training)
+            out = ops.bn_apply(y, st, relu)
+        ctx.save_for_backward(x, om, cols, y)
+        ctx.st, ctx.dcn, ctx.bn, ctx.relu = st, dcn, bn, relu
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, om, cols, y = ctx.saved_tensors
+        dcn, bn, st = ctx.dcn, ctx.bn, ctx.st
+        G, com, w = dcn.deformable_groups, dcn.conv_offset_mask, dcn.weight
+        N, H, W, C = x.shape
+        dy = _c(dout) if bn is None else ops.bn_backward(bn, st, _c(dout), y, relu=ctx.relu)
+        alpha = ops.grad_alpha(dy)
+        # the columns are the 1x1 GEMM's input: its 9C workspace columns are reduced as 9 taps x C into the OIHW rows
+        ops.conv_wgrad(dy, cols, 1, 1, 1, 0, None, None, rows=[(0, w.shape[0], ops.grad_of(w), _conv_ld(w))],
+                       red_taps=9)
+        ops.grad_of(dcn.bias).add_(dy.sum((0, 1, 2), dtype=torch.float32), alpha=alpha)
+        dx32, dom = ops.dcn_cols_bwd(_dcn_cols_grad(dy, w), x, om, G, True)
+        dx = dx32.to(x.dtype)
+        n_om = com.weight.shape[0]
+        ops.conv_wgrad(dom, x, 3, 3, 1, 1, None, None,
+                       rows=[(0, n_om, ops.grad_of(com.weight), _conv_ld(com.weight))])
+        ops.grad_of(com.bias).add_(dom[..., :n_om].sum((0, 1, 2), dtype=torch.float32), alpha=alpha)
+        wo, _ = ops.dcn_offset_rows(com.weight, com.bias, om.shape[3])
+        ops.conv_dgrad(dom, ops.pack_weight(wo, x.dtype, 1), C, H, W, 3, 3, 1, 1, out=dx, accumulate=True)
+        grads_ready(*([dcn] if bn is None else [dcn, bn]))
+        return dx, None, None, None, None
+
+
+class DeformConvV2Fn(torch.autograd.Function):
+    """dcn_v2_conv (dcn_v2.py:14-92 of the reference) on NHWC tensors: offset (N,H,W,18G) and mask (N,H,W,9G) are
+    inputs, every tensor input gets its gradient back."""
+
+    @staticmethod
+    def forward(ctx, x, offset, mask, weight, bias, G):
+        ops._need_gpu(x, offset, mask, weight, bias)
+        N, H, W, _ = x.shape
+        P = ops.dcn_om_channels(G, x.dtype)
+        om = torch.zeros(N, H, W, P, dtype=x.dtype, device=x.device)
+        om[..., :18 * G] = offset
+        om[..., 18 * G:27 * G] = mask
+        cols, y = _dcn_conv_fwd(x, om, G, False, weight, bias)
+        ctx.save_for_backward(x, om, cols, weight)
+        ctx.G = G
+        return y
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, om, cols, w = ctx.saved_tensors
+        G = ctx.G
+        dy = _c(dout)
+        dw = torch.zeros_like(w)
+        # on the current stream: autograd hands dw on as soon as this returns
+        ops._conv_wgrad(dy, cols, 1, 1, 1, 0, None, None, rows=[(0, w.shape[0], dw, _conv_ld(w))], red_taps=9)
+        db = dy.sum((0, 1, 2), dtype=torch.float32) * ops.grad_alpha(dy)
+        dx32, dom = ops.dcn_cols_bwd(_dcn_cols_grad(dy, w), x, om, G, False)
+        return (dx32.to(x.dtype), dom[..., :18 * G].contiguous(), dom[..., 18 * G:27 * G].contiguous(), dw, db, None)
 
 
 class HeadsFn(torch.autograd.Function):

@@ -101,6 +101,28 @@ class FoldedDeconv:
         return ops.deconv_fwd_res(x, self.w, self.Co, self.k, self.stride, self.pad, self.b, None, True)
 
 
+class FoldedDeform:
+    """DCN + BatchNorm2d + ReLU (a ResNet-DCN stage): the offset conv with its bias, the sampled columns
+    (``scd_dcn_cols``), then one 1x1 GEMM over them with BN folded into the operand, plus bias and ReLU."""
+
+    def __init__(self, dcn, bn, dtype):
+        _need_cuda(dcn.weight, "DCN")
+        com = dcn.conv_offset_mask
+        self.G, self.Co = dcn.deformable_groups, dcn.weight.shape[0]
+        self.P = ops.dcn_om_channels(self.G, dtype)
+        wo, bo = ops.dcn_offset_rows(com.weight, com.bias, self.P)
+        self.wo, self.bo = _pack(wo, dtype, 0), bo.detach().float().contiguous()
+        w, b = fold_conv_bn(dcn.weight, bn, conv_bias=dcn.bias)
+        self.w, self.b = _pack(w, dtype, 0), b
+        self.dtype = dtype
+
+    @torch.no_grad()
+    def __call__(self, x):
+        om = ops.conv_fwd_res(x, self.wo, self.P, 3, 3, 1, 1, self.bo, None, False)
+        cols = ops.dcn_cols(x, om, self.G, True)
+        return ops.conv_fwd_res(cols, self.w, self.Co, 1, 1, 1, 0, self.b, None, True)
+
+
 def fold_block(blk, dtype):
     """A BasicBlock / Bottleneck as a callable NHWC -> NHWC that owns its folded operands (packed once in `dtype`)."""
     from models.backbones.residuals import BasicBlock, Bottleneck
@@ -195,6 +217,8 @@ class FoldedResNet(torch.nn.Module):
         self.stem = _Stem(pre[0], pre[1], dtype)
         self.blocks = [FoldedBlock(blk, dtype) for layer in (m.layer1, m.layer2, m.layer3, m.layer4) for blk in layer]
         self.deconvs = [FoldedDeconv(dl[i], dl[i + 1], dtype) for i in range(0, len(dl), 3)]
+        # ResNet-DCN: the deformable stage in front of each deconv
+        self.deforms = [FoldedDeform(d[0], d[1], dtype) for d in m.deformLayers] if getattr(m, "deformable", False) else None
         if len({mod[0].weight.shape[0] for mod in mods}) == 1:
             self.heads = [_Heads(names, mods, dtype)]
         else:
@@ -211,7 +235,9 @@ class FoldedResNet(torch.nn.Module):
         h = self.stem(inp)
         for blk in self.blocks:
             h = blk(h)
-        for dc in self.deconvs:
+        for i, dc in enumerate(self.deconvs):
+            if self.deforms is not None:
+                h = self.deforms[i](h)
             h = dc(h)
         ret = {}
         for hd in self.heads:

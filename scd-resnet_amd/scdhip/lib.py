@@ -82,6 +82,8 @@ SIGNATURES = {
     "scd_pad_channels": (I, [I, P, L, I, I, P, P]),
     "scd_upsample2x_add": (I, [I, P, P, P, I, I, I, I, P]),
     "scd_upsample2x_add_bwd": (I, [I, P, P, I, I, I, I, P]),
+    "scd_dcn_cols": (I, [I, P, P, P, I, I, I, I, I, I, I, P]),
+    "scd_dcn_cols_bwd": (I, [I, P, P, P, P, P, I, I, I, I, I, I, I, P]),
     "scd_im2col_stem": (I, [I, P, P, I, I, I, I, I, I, I, I, I, I, P]),
     "scd_stem_conv_fwd": (I, [I, P, P, P, P, I, I, I, I, I, P]),
     "scd_stem_conv_wgrad_nsplit": (I, [L]),

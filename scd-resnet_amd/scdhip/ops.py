@@ -1581,6 +1581,85 @@ def upsample_add_bwd(dout):
     return dlow
 
 
+def dcn_chunk(dtype):
+    """Elements of a 16-byte chunk of `dtype`: what C/G and om's channel count P must be multiples of."""
+    return 4 if dtype == torch.float32 else 8
+
+
+def dcn_om_channels(G, dtype):
+    """27G offset/mask channels rounded up to whole 16-byte chunks: the narrowest om the kernels take."""
+    e = dcn_chunk(dtype)
+    return -(-27 * G // e) * e
+
+
+def dcn_offset_rows(weight, bias, P):
+    """A DCN's conv_offset_mask weight and bias with their 27G output rows zero-extended to om's P channels (whole
+    16-byte chunks): the offset conv then writes om's pad channels itself, as zeros."""
+    pad = P - weight.shape[0]
+    if not pad:
+        return weight, bias
+    return (torch.nn.functional.pad(weight.detach(), (0, 0, 0, 0, 0, 0, 0, pad)),
+            torch.nn.functional.pad(bias.detach(), (0, pad)))
+
+
+def _dcn_check(what, x, om, G, sigmoid):
+    if x.dim() != 4 or om.dim() != 4 or tuple(om.shape[:3]) != tuple(x.shape[:3]):
+        raise ValueError("%s: x %s and om %s must be NHWC tensors over the same pixels" % (what, tuple(x.shape),
+                                                                                         tuple(om.shape)))
+    if x.dtype not in _DT or om.dtype != x.dtype:
+        raise ValueError("%s: x %s and om %s must share one of the compute dtypes" % (what, x.dtype, om.dtype))
+    if not (x.is_contiguous() and om.is_contiguous()):
+        raise ValueError("%s: x and om must be contiguous" % what)
+    C, P, e = x.shape[3], om.shape[3], dcn_chunk(x.dtype)
+    if G < 1 or C % G or (C // G) % e:
+        raise ValueError("%s: %d channels in %d deformable groups (each group must hold a multiple of %d channels)"
+                         % (what, C, G, e))
+    if P < 27 * G or P % e:
+        raise ValueError("%s: om has %d channels (at least 27G = %d, in multiples of %d)" % (what, P, 27 * G, e))
+    if sigmoid not in (0, 1, False, True):
+        raise ValueError("%s: sigmoid must be 0 (masks) or 1 (logits)" % what)
+
+
+def dcn_cols(x, om, G=1, sigmoid=True):
+    """The sampled, modulated columns of a 3x3 / stride 1 / pad 1 deformable conv (scd_dcn_cols): x (N,H,W,C), om
+    (N,H,W,P >= 27G) with the offsets in channels [0, 18G) and the masks (sigmoid=False) or their logits
+    (sigmoid=True) in [18G, 27G) -> cols (N,H,W,9C), column k*C + c."""
+    _dcn_check("dcn_cols", x, om, G, sigmoid)
+    _need_gpu(x, om)
+    N, H, W, C = x.shape
+    cols = torch.empty(N, H, W, 9 * C, dtype=x.dtype, device=x.device)
+    t0 = ClassTimer.begin()
+    L.call("scd_dcn_cols", dt(x), ptr(x), ptr(om), ptr(cols), N, H, W, C, G, om.shape[3], int(sigmoid), stream())
+    if t0 is not None:
+        ClassTimer.end("dcn", t0, cols.numel() * cols.element_size() * 2)
+    return cols
+
+
+def dcn_cols_bwd(dcols, x, om, G=1, sigmoid=True, dx32=None):
+    """Backward of dcn_cols (scd_dcn_cols_bwd): returns (dx32, dom).  dx32 is the fp32 (N,H,W,C) input gradient, added
+    into the given buffer or a fresh zeroed one (float atomics: its last bits vary from call to call); dom (N,H,W,P)
+    is written whole in x's dtype and is bit-reproducible."""
+    _dcn_check("dcn_cols_bwd", x, om, G, sigmoid)
+    N, H, W, C = x.shape
+    if tuple(dcols.shape) != (N, H, W, 9 * C) or dcols.dtype != x.dtype or not dcols.is_contiguous():
+        raise ValueError("dcn_cols_bwd: dcols %s %s must be a contiguous (N,H,W,9C) tensor of x's dtype"
+                         % (tuple(dcols.shape), dcols.dtype))
+    if dx32 is not None and (tuple(dx32.shape) != tuple(x.shape) or dx32.dtype != torch.float32
+                             or not dx32.is_contiguous()):
+        raise ValueError("dcn_cols_bwd: dx32 %s %s must be a contiguous fp32 tensor of x's shape"
+                         % (tuple(dx32.shape), dx32.dtype))
+    _need_gpu(dcols, x, om, dx32)
+    if dx32 is None:
+        dx32 = torch.zeros(N, H, W, C, dtype=torch.float32, device=x.device)
+    dom = torch.empty_like(om)
+    t0 = ClassTimer.begin()
+    L.call("scd_dcn_cols_bwd", dt(x), ptr(dcols), ptr(x), ptr(om), ptr(dx32), ptr(dom), N, H, W, C, G, om.shape[3],
+           int(sigmoid), stream())
+    if t0 is not None:
+        ClassTimer.end("dcn", t0, dcols.numel() * dcols.element_size() * 2)
+    return dx32, dom
+
+
 def adam_step(p, g, m, v, lr, beta1, beta2, eps, step, gscale=1.0):
     bc1 = 1 - beta1 ** step
     bc2 = 1 - beta2 ** step
